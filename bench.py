@@ -23,6 +23,13 @@ Other modes: `--mode extract` (extraction + stereo only), `--mode lba` (config 3
 with the map, keyframes and synchronous LocalMapping + LocalBA on the host around the GPU
 operators -- over a rendered sequence with exact ground truth; reports frames/s and ATE).
 
+A plain run sets up, warms up, times `--steps` steps and prints the headline line.  `--full` adds
+everything measured beside it, each in runs of its own: the CPU baselines, the per-stage, phase and
+roofline profiles, the PCIe-inclusive pass, the idle-GPU keyframe latency (`--mode system`: the
+synchronous loop and the Python host loop).  `--dump-outputs DIR` writes what the last timed step
+computed as DIR/<name>.npy (float32 / float64); the inputs are seeded, so two builds run with the
+same arguments can be compared array for array.
+
 Prints ONE JSON line on rank 0 (contract: task statement; fields documented in DESIGN.md).
 """
 from __future__ import annotations
@@ -58,14 +65,21 @@ _vp = C.c_void_p
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=200)
-    ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--steps", type=int, default=200,
+                    help="timed steps.  --mode track / extract time exactly this many; --mode lba times "
+                         "max(STEPS // 10, 3) LocalBAs, --mode batch max(STEPS // 10, 5) launches of --batch frames, "
+                         "--mode system tracks max(STEPS, 12) frames and times all but the first 10; the line's "
+                         "'steps' is the number timed")
+    ap.add_argument("--warmup", type=int, default=20,
+                    help="untimed steps before them (--mode lba: max(WARMUP // 10, 1) LocalBAs, --mode batch: "
+                         "max(WARMUP // 4, 2) launches, --mode system: its first 10 frames)")
     ap.add_argument("--mode", choices=["track", "extract", "lba", "batch", "system"], default="track")
     ap.add_argument("--frames", type=int, default=8, help="distinct stereo frames resident per rank")
     ap.add_argument("--nfeatures", type=int, default=2000)
     ap.add_argument("--batch", type=int, default=64, help="frames per launch in --mode batch")
     ap.add_argument("--cpu-sample-s", type=float, default=15.0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full: leave the CPU baselines out (a plain run has none)")
     ap.add_argument("--lm-chain", choices=["full", "bow-ba"], default="full",
                     help="per-keyframe LocalMapping work: the whole LocalMapping::Run body, or ComputeBoW + LocalBA")
     ap.add_argument("--dist-backend", default="nccl",
@@ -79,6 +93,13 @@ def parse():
     ap.add_argument("--frame-events", action="store_true",
                     help="track mode: HIP events around every timed frame's extraction and tracking (their "
                          "overlap in the JSON line's 'overlap'; diagnostics, adds four events per frame)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline figure: the CPU baselines, the per-stage, phase "
+                         "and roofline profiles, the PCIe-inclusive pass, the other configurations of a mode")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy "
+                         "(float32 / float64).  Reproducible run to run in every mode but --mode system, whose "
+                         "concurrent LocalMapping makes the trajectory depend on timing")
     ap.add_argument("--print-traffic-config", action="store_true",
                     help="print the workload key tools/pmc_traffic.py stores with a traffic summary, and exit")
     return ap.parse_args()
@@ -196,6 +217,33 @@ def lba_trial_traffic(a):
 def read_traffic(path, name, config=None):
     per = _traffic_summary(path, config)
     return None if per is None else per.get(name)
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def keypoints_f32(kps):
+    """cv::KeyPoint records (n x 7 int32 words: x, y, size, angle, response as float bits, octave,
+    class_id) as n x 7 float32 values."""
+    kps = np.ascontiguousarray(kps, np.int32).reshape(-1, 7)
+    out = np.empty(kps.shape, np.float32)
+    out[:, :5] = kps[:, :5].view(np.float32)
+    out[:, 5:] = kps[:, 5:]
+    return out
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: each array as DIR/<name>.npy, float64 as it is and everything else as
+    float32 (indices, counts, flags, descriptor bytes and octaves are all below 2^24: exact)."""
+    os.makedirs(path, exist_ok=True)
+    total = 0
+    for name, v in arrays.items():
+        v = np.asarray(v)
+        v = np.ascontiguousarray(v, np.float64 if v.dtype == np.float64 else np.float32)
+        total += v.nbytes
+        if total > DUMP_LIMIT_BYTES:
+            raise RuntimeError(f"--dump-outputs: {name} takes the dump past {DUMP_LIMIT_BYTES} bytes")
+        np.save(os.path.join(path, name + ".npy"), v)
 
 
 # --------------------------------------------------------------------------------- track
@@ -346,6 +394,71 @@ def cpu_local_mapping(O, vocab, job):
     return n_new
 
 
+def track_outputs(tr, mapper):
+    """What a caller of the timed path holds after its last step (--dump-outputs): the last
+    tracked frame's features and stereo matches, its matches, outlier flags, poses and counts, and
+    what the last keyframe's LocalMapping chain found and its LocalBA returned."""
+    r = tr.results()
+    nl, nr = (int(x) for x in tr.counts.cpu().numpy())
+    kps, desc = tr.kps.cpu().numpy(), tr.desc.cpu().numpy()
+    out = {"left_keypoints": keypoints_f32(kps[0, :nl]), "right_keypoints": keypoints_f32(kps[1, :nr]),
+           "left_descriptors": desc[0, :nl], "right_descriptors": desc[1, :nr],
+           "u_right": tr.u_right[0, :nl].cpu().numpy(), "depth": tr.depth[0, :nl].cpu().numpy(),
+           "match_last_frame": tr.match_lf[:nl].cpu().numpy(), "match_local_map": tr.match_mp[:nl].cpu().numpy(),
+           "outlier": tr.outlier[:nl].cpu().numpy(), "tcw_motion_model": r["tcw_mm"], "tcw": r["tcw"],
+           "track_counts": [r["search_matches"], r["outliers_mm"], r["nmatches_map"], r["inliers"], r["outliers"]]}
+    ba = mapper.last
+    if ba is not None:
+        out.update({"local_ba_tcw": ba["tcw"], "local_ba_points": ba["pos"], "local_ba_erase": ba["erase"],
+                    "local_ba_chi2": np.array(ba["chi2"], np.float64), "local_ba_iterations": ba["iterations"]})
+    o = mapper.last_job_outputs()
+    if o is not None:  # CreateNewMapPoints' pairs and accepted points, the Fuse searches' candidates
+        out.update({"triangulation_match": o["tri"], "triangulation_ok": o["tri_ok"], "new_points": o["x3d"],
+                    "fuse_match": o["fuse_match"]})
+    return out
+
+
+def pcie_inclusive_pass(a, S, tr, step, sync, ext, h_imgs, dist, world):
+    """The PCIe-inclusive pass (not `value`: the contract's value has the inputs resident in HBM):
+    the same steps with each stereo pair DMA'd from pinned host memory, overlapped with the
+    previous frame's tracking; and the DMA alone, synchronised, per pair."""
+    rows, cols, F = S["cam"].height, S["cam"].width, a.frames
+    img_bytes = rows * cols
+    ext_ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
+    sync()
+    ext_ev[0].record(ext)
+    for i in range(16):
+        tr.extract_stereo(S["imgs"].data_ptr() + (2 + i % F) * 2 * img_bytes, rows, cols)
+    ext_ev[1].record(ext)
+    for i in range(16):
+        tr.extract_stereo(h_imgs.ptr + (2 + i % F) * 2 * img_bytes, rows, cols, host=True)
+    ext_ev[2].record(ext)
+    sync()
+    upload_ms = (ext_ev[1].elapsed_time(ext_ev[2]) - ext_ev[0].elapsed_time(ext_ev[1])) / 16
+    if dist:
+        dist.barrier()
+    sync()
+    t0 = time.perf_counter()
+    host_up = 0.0
+    for i in range(a.steps):
+        th = time.perf_counter()
+        step(i, host=True)
+        host_up += time.perf_counter() - th
+    t_enq_up = time.perf_counter() - t0
+    sync()
+    if dist:
+        dist.barrier()
+    dt_up = max_over_ranks(time.perf_counter() - t0, dist)
+    return {"value": round(a.steps * world / dt_up, 3), "unit": "frames/s", "ms_per_step": round(dt_up / a.steps * 1e3, 4),
+            "upload_bytes_per_frame": 2 * img_bytes,
+            "host_enqueue_ms_per_step": round(host_up / a.steps * 1e3, 4),
+            "host_enqueued_all_ms": round(t_enq_up * 1e3, 3), "upload_ms_per_frame_alone": round(upload_ms, 4),
+            "upload_GBps_alone": round(2 * img_bytes / (upload_ms * 1e-3) / 1e9, 2),
+            "how": "each step's stereo pair read from pinned host memory by a copy kernel on the extraction stream "
+                   "(orbmi_extract_batch_host), ahead of its extraction and overlapped with the previous frame's "
+                   "tracking; upload_ms_per_frame_alone = extraction from host minus from HBM, back to back"}
+
+
 def run_track(a, rank, world, local, dist):
     from orb_slam2_with_comment_amd import synth_map as SM
     from orb_slam2_with_comment_amd.pipeline import LocalMapper, StreamExchange
@@ -383,9 +496,11 @@ def run_track(a, rank, world, local, dist):
 
     # the same frames in pinned host memory: the PCIe-inclusive pass DMAs each step's stereo pair
     # to HBM on the extraction stream (stereo_kitti.cc:81-97 times TrackStereo from a host image)
-    from orb_slam2_with_comment_amd import _hip
-    h_imgs = _hip.PinnedBytes(S["imgs"].numel())
-    h_imgs.array[:] = S["imgs"].cpu().numpy().reshape(-1)
+    h_imgs = None
+    if a.full:
+        from orb_slam2_with_comment_amd import _hip
+        h_imgs = _hip.PinnedBytes(S["imgs"].numel())
+        h_imgs.array[:] = S["imgs"].cpu().numpy().reshape(-1)
 
     def step(i, host=False):
         f = 2 + i % F
@@ -407,72 +522,76 @@ def run_track(a, rank, world, local, dist):
     for i in range(a.warmup):
         step(i)
     sync()
-    # one keyframe alone (the LocalMapping chain): its latency on an otherwise idle GPU
-    t0 = time.perf_counter()
-    keyframe(2)
-    mapper.wait()
-    lba_ms = (time.perf_counter() - t0) * 1e3
-    lba_info = mapper.last
-    chain_info = dict(mapper.last_chain.materialize()) if full_chain else None
-    t0 = time.perf_counter()
-    for _ in range(10):
-        b = mapper.bow
-        voc.transform_device(kf_desc(2)[0], kf_desc(2)[1], None, 4, b["word"].data_ptr(), b["value"].data_ptr(),
-                             b["node"].data_ptr(), b["off"].data_ptr(), b["feat"].data_ptr(), b["counts"].data_ptr())
-        voc.synchronize()
-    bow_us = (time.perf_counter() - t0) / 10 * 1e6
-    bow_words = int(mapper.bow["counts"][0])
+    full = a.full  # everything beside the headline figure (a plain run only times the steps)
+    if full:
+        # one keyframe alone (the LocalMapping chain): its latency on an otherwise idle GPU
+        t0 = time.perf_counter()
+        keyframe(2)
+        mapper.wait()
+        lba_ms = (time.perf_counter() - t0) * 1e3
+        lba_info = mapper.last
+        chain_info = dict(mapper.last_chain.materialize()) if full_chain else None
+        t0 = time.perf_counter()
+        for _ in range(10):
+            b = mapper.bow
+            voc.transform_device(kf_desc(2)[0], kf_desc(2)[1], None, 4, b["word"].data_ptr(), b["value"].data_ptr(),
+                                 b["node"].data_ptr(), b["off"].data_ptr(), b["feat"].data_ptr(),
+                                 b["counts"].data_ptr())
+            voc.synchronize()
+        bow_us = (time.perf_counter() - t0) / 10 * 1e6
+        bow_words = int(mapper.bow["counts"][0])
 
-    # per-stage profile (untimed): extractor stages via the library's event brackets
-    stage = profile_stages(tr.extractor.handle, lambda i: (tr.extract_stereo(
-        S["imgs"].data_ptr() + (2 + i % F) * 2 * img_bytes, rows, cols), tr.synchronize()), max(F, 16))
-    # phase profile (untimed): HIP events on the tracking stream around each phase
-    n_tr = max(F, 32)
-    phases = {"extract_stereo": 0.0, "track_motion_model": 0.0, "track_local_map": 0.0}
-    tr.synchronize()
-    t0 = time.perf_counter()
-    for i in range(n_tr):
-        f = 2 + i % F
-        ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
-        ev[0].record(ext)
-        tr.extract_stereo(S["imgs"].data_ptr() + f * 2 * img_bytes, rows, cols)
-        ev[1].record(ext)
-        trk.wait_event(ev[1])
-        tr.track_with_motion_model(S["tcws"][f], S["lf_views"][f - 1], S["lf_pts"][f - 1].data_ptr())
-        ev[2].record(trk)
-        tr.track_local_map(S["lf_views"][f - 1], S["lf_pts"][f - 1].data_ptr(), S["mps"][f].data_ptr(),
-                           S["n_mp"][f])
-        ev[3].record(trk)
+        # per-stage profile (untimed): extractor stages via the library's event brackets
+        stage = profile_stages(tr.extractor.handle, lambda i: (tr.extract_stereo(
+            S["imgs"].data_ptr() + (2 + i % F) * 2 * img_bytes, rows, cols), tr.synchronize()), max(F, 16))
+        # phase profile (untimed): HIP events on the tracking stream around each phase
+        n_tr = max(F, 32)
+        phases = {"extract_stereo": 0.0, "track_motion_model": 0.0, "track_local_map": 0.0}
         tr.synchronize()
-        for k, name in enumerate(phases):
-            phases[name] += ev[k].elapsed_time(ev[k + 1]) / n_tr
-    track_only_ms = (time.perf_counter() - t0) / n_tr * 1e3  # includes a host sync per frame
-    # tracking alone, back to back (no LocalBA): host enqueue time vs GPU-bound time per frame
-    tr.synchronize()
-    t0 = time.perf_counter()
-    for i in range(n_tr):
-        f = 2 + i % F
-        tr.track(S["imgs"].data_ptr() + f * 2 * img_bytes, rows, cols, S["tcws"][f], S["lf_views"][f - 1],
-                 S["lf_pts"][f - 1].data_ptr(), S["mps"][f].data_ptr(), S["n_mp"][f])
-    enqueue_ms = (time.perf_counter() - t0) / n_tr * 1e3
-    tr.synchronize()
-    track_async_ms = (time.perf_counter() - t0) / n_tr * 1e3
-    outcome = tr.results()
-    nm_lf = int((tr.match_lf[:int(tr.counts[0])] >= 0).sum())
-    nm_mp = int((tr.match_mp[:int(tr.counts[0])] >= 0).sum())
-    kp_per_frame = float(stage["kp_per_step"])
+        t0 = time.perf_counter()
+        for i in range(n_tr):
+            f = 2 + i % F
+            ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
+            ev[0].record(ext)
+            tr.extract_stereo(S["imgs"].data_ptr() + f * 2 * img_bytes, rows, cols)
+            ev[1].record(ext)
+            trk.wait_event(ev[1])
+            tr.track_with_motion_model(S["tcws"][f], S["lf_views"][f - 1], S["lf_pts"][f - 1].data_ptr())
+            ev[2].record(trk)
+            tr.track_local_map(S["lf_views"][f - 1], S["lf_pts"][f - 1].data_ptr(), S["mps"][f].data_ptr(),
+                               S["n_mp"][f])
+            ev[3].record(trk)
+            tr.synchronize()
+            for k, name in enumerate(phases):
+                phases[name] += ev[k].elapsed_time(ev[k + 1]) / n_tr
+        track_only_ms = (time.perf_counter() - t0) / n_tr * 1e3  # includes a host sync per frame
+        # tracking alone, back to back (no LocalBA): host enqueue time vs GPU-bound time per frame
+        tr.synchronize()
+        t0 = time.perf_counter()
+        for i in range(n_tr):
+            f = 2 + i % F
+            tr.track(S["imgs"].data_ptr() + f * 2 * img_bytes, rows, cols, S["tcws"][f], S["lf_views"][f - 1],
+                     S["lf_pts"][f - 1].data_ptr(), S["mps"][f].data_ptr(), S["n_mp"][f])
+        enqueue_ms = (time.perf_counter() - t0) / n_tr * 1e3
+        tr.synchronize()
+        track_async_ms = (time.perf_counter() - t0) / n_tr * 1e3
+        outcome = tr.results()
+        nm_lf = int((tr.match_lf[:int(tr.counts[0])] >= 0).sum())
+        nm_mp = int((tr.match_mp[:int(tr.counts[0])] >= 0).sum())
+        kp_per_frame = float(stage["kp_per_step"])
 
     # ---- timed region
-    dom = stage["dominant"]
     lib = __import__("orb_slam2_with_comment_amd._capi", fromlist=["lib"]).lib()
-    lib.orbmi_set_profiling(tr.extractor.handle, 1 << stage["dominant_id"])
-    reset_profile(tr.extractor.handle)
-    # the path's dominant kernel (rocprofv3, profiles/): PoseOptimization, bracketed with HIP
-    # events on the tracking stream it is launched on
-    # (every POSE_PROF_STRIDE-th launch: a timed event pair is two queue packets of ~6 µs each on
-    # the tracking stream; an odd stride alternates TrackWithMotionModel's and TrackLocalMap's)
-    lib.orbmi_pose_set_profiling(tr.pose._h, POSE_PROF_STRIDE)
-    pose_prof = read_pose_profile(lib, tr.pose._h)
+    if full:
+        dom = stage["dominant"]
+        lib.orbmi_set_profiling(tr.extractor.handle, 1 << stage["dominant_id"])
+        reset_profile(tr.extractor.handle)
+        # the path's dominant kernel (rocprofv3, profiles/): PoseOptimization, bracketed with HIP
+        # events on the tracking stream it is launched on
+        # (every POSE_PROF_STRIDE-th launch: a timed event pair is two queue packets of ~6 µs each on
+        # the tracking stream; an odd stride alternates TrackWithMotionModel's and TrackLocalMap's)
+        lib.orbmi_pose_set_profiling(tr.pose._h, POSE_PROF_STRIDE)
+        pose_prof = read_pose_profile(lib, tr.pose._h)
     sync()
     if dist:
         dist.barrier()
@@ -496,11 +615,14 @@ def run_track(a, rank, world, local, dist):
     if dist:
         dist.barrier()
     dt = time.perf_counter() - t0
-    ms, nl = read_profile(tr.extractor.handle)
-    lib.orbmi_set_profiling(tr.extractor.handle, 0)
-    pose_prof = read_pose_profile(lib, tr.pose._h)
-    lib.orbmi_pose_set_profiling(tr.pose._h, 0)
+    if full:
+        ms, nl = read_profile(tr.extractor.handle)
+        lib.orbmi_set_profiling(tr.extractor.handle, 0)
+        pose_prof = read_pose_profile(lib, tr.pose._h)
+        lib.orbmi_pose_set_profiling(tr.pose._h, 0)
     dt = max_over_ranks(dt, dist)
+    if a.dump_outputs and rank == 0:  # the last timed step's results, before anything else runs
+        dump_outputs(a.dump_outputs, track_outputs(tr, mapper))
     overlap = frame_overlap(tr.frame_events) if tr.frame_events else None
     if overlap:
         overlap.update({"host_enqueued_ms": round((t_enq - t0) * 1e3, 3), "tracking_done_ms": round((t_trk - t0) * 1e3, 3),
@@ -509,56 +631,23 @@ def run_track(a, rank, world, local, dist):
         overlap.update(job_overlap(mapper.job_events))
     tr.frame_events = None
     mapper.job_events = None
-    # the PCIe-inclusive pass (not `value`: the contract's value has the inputs resident in HBM):
-    # the same steps with each stereo pair DMA'd from pinned host memory, overlapped with the
-    # previous frame's tracking; and the DMA alone, synchronised, per pair
-    ext_ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
-    sync()
-    ext_ev[0].record(ext)
-    for i in range(16):
-        tr.extract_stereo(S["imgs"].data_ptr() + (2 + i % F) * 2 * img_bytes, rows, cols)
-    ext_ev[1].record(ext)
-    for i in range(16):
-        tr.extract_stereo(h_imgs.ptr + (2 + i % F) * 2 * img_bytes, rows, cols, host=True)
-    ext_ev[2].record(ext)
-    sync()
-    upload_ms = (ext_ev[1].elapsed_time(ext_ev[2]) - ext_ev[0].elapsed_time(ext_ev[1])) / 16
-    if dist:
-        dist.barrier()
-    sync()
-    t0 = time.perf_counter()
-    host_up = 0.0
-    for i in range(a.steps):
-        th = time.perf_counter()
-        step(i, host=True)
-        host_up += time.perf_counter() - th
-    t_enq_up = time.perf_counter() - t0
-    sync()
-    if dist:
-        dist.barrier()
-    dt_up = max_over_ranks(time.perf_counter() - t0, dist)
-    pcie = {"value": round(a.steps * world / dt_up, 3), "unit": "frames/s", "ms_per_step": round(dt_up / a.steps * 1e3, 4),
-            "upload_bytes_per_frame": 2 * img_bytes,
-            "host_enqueue_ms_per_step": round(host_up / a.steps * 1e3, 4),
-            "host_enqueued_all_ms": round(t_enq_up * 1e3, 3), "upload_ms_per_frame_alone": round(upload_ms, 4),
-            "upload_GBps_alone": round(2 * img_bytes / (upload_ms * 1e-3) / 1e9, 2),
-            "how": "each step's stereo pair read from pinned host memory by a copy kernel on the extraction stream "
-                   "(orbmi_extract_batch_host), ahead of its extraction and overlapped with the previous frame's "
-                   "tracking; upload_ms_per_frame_alone = extraction from host minus from HBM, back to back"}
+    if full:
+        pcie = pcie_inclusive_pass(a, S, tr, step, sync, ext, h_imgs, dist, world)
     n_lba = (a.steps + KF_EVERY - 1) // KF_EVERY
     x_matches = None
     if xch is not None:
         xch.synchronize()
         x_matches = int((xch.xmatch[:int(tr.counts[0])] >= 0).sum())
     value = a.steps * world / dt
-    ext_roof = roofline_entry(dom, stage, ms[stage["dominant_id"]], nl[stage["dominant_id"]], a.traffic,
-                              traffic_config(a))
-    roof = pose_roofline(pose_prof, outcome["recs"], a.traffic, traffic_config(a))
+    if full:
+        ext_roof = roofline_entry(dom, stage, ms[stage["dominant_id"]], nl[stage["dominant_id"]], a.traffic,
+                                  traffic_config(a))
+        roof = pose_roofline(pose_prof, outcome["recs"], a.traffic, traffic_config(a))
     out = None
     if rank == 0:
         cpu = None
         cpu_tp = None
-        if not a.no_cpu_baseline and world == 1:
+        if full and not a.no_cpu_baseline and world == 1:
             cpu = cpu_baseline_track(S, problem, a)
             O = oracle_native()
             imgs = [x for fr in S["feats"] for x in fr[:2]]
@@ -588,40 +677,45 @@ def run_track(a, rank, world, local, dist):
                                if world > 1 else ""),
                 "frames_resident": F, "parallelism": f"one stereo stream per GPU x{world}",
             },
-            "kpts_desc_per_s": round(value * kp_per_frame, 1),
-            "keypoints_per_frame": round(kp_per_frame, 1),
+            "full": full,
             "host_enqueue_ms_per_step_timed": round(host_s / a.steps * 1e3, 4),
-            "pcie_inclusive": pcie,
             **({"overlap": overlap} if overlap else {}),
-            "matches_per_frame": {"last_frame": nm_lf, "local_map": nm_mp, "inliers": outcome["inliers"],
-                                  "tracking_ok": outcome["ok"]},
-            "phase_ms_per_frame": {k: round(v, 4) for k, v in phases.items()},
             "cross_stream_matches_last_frame": x_matches,
-            "track_only_ms_per_frame_synced": round(track_only_ms, 4),
-            "track_only_ms_per_frame_back_to_back": round(track_async_ms, 4),
-            "host_enqueue_ms_per_frame": round(enqueue_ms, 4),
-            "compute_bow": {"us_per_keyframe_synced": round(bow_us, 1), "words": bow_words,
-                            "vocabulary": "synthetic k=10 L=6 (1,111,111 nodes), L1 / TF-IDF, levelsup 4"},
-            "local_mapping": {"ms_per_keyframe_idle_gpu": round(lba_ms, 3), "chain": a.lm_chain,
-                              "keyframes_in_timed_region": n_lba, "last_keyframe": chain_info,
-                              "compute_bow_issued_ahead": getattr(mapper, "bow_ahead", 0)},
-            "local_ba": {"calls_in_timed_region": n_lba,
-                         "iterations": list(lba_info["iterations"]) if lba_info else None,
-                         "edges": int(len(problem.edges)), "points": int(len(problem.pts)),
-                         "keyframes": int(len(problem.kfs))},
-            "stage_ms_per_step": stage["stage_ms"],
-            "roofline": roof,
-            "extractor_roofline": ext_roof,
-            "pipeline_roofline": pipeline_roofline(stage, rows, cols),
-            "cpu_baseline": cpu,
-            "cpu_baseline_throughput": cpu_tp,
             "host": host_info(),
         }
+        if full:
+            out.update({
+                "kpts_desc_per_s": round(value * kp_per_frame, 1),
+                "keypoints_per_frame": round(kp_per_frame, 1),
+                "pcie_inclusive": pcie,
+                "matches_per_frame": {"last_frame": nm_lf, "local_map": nm_mp, "inliers": outcome["inliers"],
+                                      "tracking_ok": outcome["ok"]},
+                "phase_ms_per_frame": {k: round(v, 4) for k, v in phases.items()},
+                "track_only_ms_per_frame_synced": round(track_only_ms, 4),
+                "track_only_ms_per_frame_back_to_back": round(track_async_ms, 4),
+                "host_enqueue_ms_per_frame": round(enqueue_ms, 4),
+                "compute_bow": {"us_per_keyframe_synced": round(bow_us, 1), "words": bow_words,
+                                "vocabulary": "synthetic k=10 L=6 (1,111,111 nodes), L1 / TF-IDF, levelsup 4"},
+                "local_mapping": {"ms_per_keyframe_idle_gpu": round(lba_ms, 3), "chain": a.lm_chain,
+                                  "keyframes_in_timed_region": n_lba, "last_keyframe": chain_info,
+                                  "compute_bow_issued_ahead": getattr(mapper, "bow_ahead", 0)},
+                "local_ba": {"calls_in_timed_region": n_lba,
+                             "iterations": list(lba_info["iterations"]) if lba_info else None,
+                             "edges": int(len(problem.edges)), "points": int(len(problem.pts)),
+                             "keyframes": int(len(problem.kfs))},
+                "stage_ms_per_step": stage["stage_ms"],
+                "roofline": roof,
+                "extractor_roofline": ext_roof,
+                "pipeline_roofline": pipeline_roofline(stage, rows, cols),
+                "cpu_baseline": cpu,
+                "cpu_baseline_throughput": cpu_tp,
+            })
     if xch is not None:
         xch.close()
     mapper.close()
     tr.close()
-    h_imgs.close()
+    if h_imgs is not None:
+        h_imgs.close()
     return out
 
 
@@ -840,11 +934,12 @@ def run_extract(a, rank, world, local, dist):
     for i in range(a.warmup):
         step(i)
     tr.synchronize()
-    stage = profile_stages(tr.extractor.handle, lambda i: (step(i), tr.synchronize()), max(a.frames, 16))
     from orb_slam2_with_comment_amd import _capi
     lib = _capi.lib()
-    lib.orbmi_set_profiling(tr.extractor.handle, 1 << stage["dominant_id"])
-    reset_profile(tr.extractor.handle)
+    if a.full:
+        stage = profile_stages(tr.extractor.handle, lambda i: (step(i), tr.synchronize()), max(a.frames, 16))
+        lib.orbmi_set_profiling(tr.extractor.handle, 1 << stage["dominant_id"])
+        reset_profile(tr.extractor.handle)
     tr.synchronize()
     if dist:
         dist.barrier()
@@ -856,12 +951,20 @@ def run_extract(a, rank, world, local, dist):
     if dist:
         dist.barrier()
     dt = max_over_ranks(time.perf_counter() - t0, dist)
-    ms, nl = read_profile(tr.extractor.handle)
-    lib.orbmi_set_profiling(tr.extractor.handle, 0)
+    if a.full:
+        ms, nl = read_profile(tr.extractor.handle)
+        lib.orbmi_set_profiling(tr.extractor.handle, 0)
+    if a.dump_outputs and rank == 0:
+        nl_, nr_ = (int(x) for x in tr.counts.cpu().numpy())
+        kps, desc = tr.kps.cpu().numpy(), tr.desc.cpu().numpy()
+        dump_outputs(a.dump_outputs, {
+            "left_keypoints": keypoints_f32(kps[0, :nl_]), "right_keypoints": keypoints_f32(kps[1, :nr_]),
+            "left_descriptors": desc[0, :nl_], "right_descriptors": desc[1, :nr_],
+            "u_right": tr.u_right[0, :nl_].cpu().numpy(), "depth": tr.depth[0, :nl_].cpu().numpy()})
     value = a.steps * world / dt
     out = None
     if rank == 0:
-        cpu = None if (a.no_cpu_baseline or world > 1) else cpu_baseline_extract(frames, cam, a)
+        cpu = None if (not a.full or a.no_cpu_baseline or world > 1) else cpu_baseline_extract(frames, cam, a)
         out = {
             "metric": METRIC, "value": round(value, 3), "unit": "frames/s", "n_gpus": world, "steps": a.steps,
             "warmup": a.warmup, "ms_per_step": round(dt / a.steps * 1e3, 4), "higher_is_better": True,
@@ -869,14 +972,18 @@ def run_extract(a, rank, world, local, dist):
             "data": "synthetic: ray-cast KITTI-shaped 1241x376 stereo sequence, resident in HBM",
             "config": {"workload": "extraction only: ORBextractor(L,R) [2000 feat] + ComputeStereoMatches",
                        "frames_resident": a.frames, "parallelism": f"one stereo stream per GPU x{world}"},
-            "kpts_desc_per_s": round(value * stage["kp_per_step"], 1),
-            "keypoints_per_frame": stage["kp_per_step"],
-            "stage_ms_per_step": stage["stage_ms"],
-            "roofline": roofline_entry(stage["dominant"], stage, ms[stage["dominant_id"]], nl[stage["dominant_id"]],
-                                       a.traffic, traffic_config(a)),
-            "pipeline_roofline": pipeline_roofline(stage, rows, cols),
-            "cpu_baseline": cpu, "host": host_info(),
+            "full": a.full, "host": host_info(),
         }
+        if a.full:
+            out.update({
+                "kpts_desc_per_s": round(value * stage["kp_per_step"], 1),
+                "keypoints_per_frame": stage["kp_per_step"],
+                "stage_ms_per_step": stage["stage_ms"],
+                "roofline": roofline_entry(stage["dominant"], stage, ms[stage["dominant_id"]],
+                                           nl[stage["dominant_id"]], a.traffic, traffic_config(a)),
+                "pipeline_roofline": pipeline_roofline(stage, rows, cols),
+                "cpu_baseline": cpu,
+            })
     tr.close()
     return out
 
@@ -921,10 +1028,14 @@ def run_lba(a, rank, world, local, dist):
     if dist:
         dist.barrier()
     dt = max_over_ranks(time.perf_counter() - t0, dist)
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, {"local_ba_tcw": res["tcw"], "local_ba_points": res["pos"],
+                                      "local_ba_erase": res["erase"], "local_ba_iterations": res["iterations"],
+                                      "local_ba_chi2": np.array(res["chi2"], np.float64)})
     out = None
     if rank == 0:
         cpu = None
-        if not a.no_cpu_baseline and world == 1:
+        if a.full and not a.no_cpu_baseline and world == 1:
             O = oracle_native()
             n, t0 = 0, time.perf_counter()
             while True:
@@ -1008,7 +1119,8 @@ def run_system(a, rank, world, local, dist):
         wait_s = time.perf_counter() - t0
         torch.cuda.synchronize()
         gt = np.array([fr[2] for fr in frames])
-        ate = ate_rmse(slam.trajectory_twc(), gt)
+        traj = np.array(slam.trajectory_twc())
+        ate = ate_rmse(traj, gt)
         st = slam.stats
         ok = sum(1 for x in st if x.get("state") == 2)
         counts = slam.counts()
@@ -1019,18 +1131,21 @@ def run_system(a, rank, world, local, dist):
         counts["local_mapping_ms_per_keyframe"] = {k[3:]: round(v * per_kf, 4) for k, v in ph.items()
                                                    if k.startswith("lm_")}
         slam.Shutdown()
-        return times, wait_s, ate, ok, counts
+        return times, wait_s, ate, ok, counts, traj, np.array([x.get("state", -1) for x in st])
 
     # the product configuration: LocalMapping on its own thread, concurrent with Tracking as in
-    # the reference (System::System starts it, src/System.cc:84-92); then the synchronous form
-    # (deterministic, what the parity tests drive) for comparison
-    times, wait_s, ate, ok, counts = run_native(True)
+    # the reference (System::System starts it, src/System.cc:84-92); then (--full) the synchronous
+    # form (deterministic, what the parity tests drive) for comparison
+    times, wait_s, ate, ok, counts, traj, states = run_native(True)
     dt = max_over_ranks(float(times[W:].sum()) + wait_s, dist)
-    s_times, s_wait, s_ate, s_ok, s_counts = run_native(False)
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, {"trajectory_twc": traj, "frame_state": states})
+    if a.full:
+        s_times, s_wait, s_ate, s_ok, s_counts, _, _ = run_native(False)
     out = None
     if rank == 0:
         cpu = py = None
-        if not a.no_cpu_baseline and world == 1:
+        if a.full and not a.no_cpu_baseline and world == 1:
             from slam_backends import OracleBackend
             O = oracle_native()  # the -O3 -march=native build, loaded before the backend binds it
             ref = StereoSLAM(s, backend=OracleBackend(s, voc))
@@ -1082,7 +1197,10 @@ def run_system(a, rank, world, local, dist):
             "phase_ms_per_frame": counts["phase_ms_per_frame"],
             "local_mapping_ms_per_keyframe": counts["local_mapping_ms_per_keyframe"],
             "final_local_mapping_wait_ms": round(wait_s * 1e3, 3),
-            "synchronous_local_mapping": {
+            "full": a.full, "host": host_info(),
+        }
+        if a.full:
+            out.update({"synchronous_local_mapping": {
                 "frames_per_s": round((N - W) / (float(s_times[W:].sum()) + s_wait), 3),
                 "frame_ms": {"median": round(float(np.median(s_times[W:])) * 1e3, 3),
                              "mean": round(float(np.mean(s_times[W:])) * 1e3, 3),
@@ -1091,8 +1209,7 @@ def run_system(a, rank, world, local, dist):
                 "local_ba_calls": s_counts["local_ba_calls"], "phase_ms_per_frame": s_counts["phase_ms_per_frame"],
                 "local_mapping_outcomes": s_counts["local_mapping_outcomes"],
                 "local_mapping_ms_per_keyframe": s_counts["local_mapping_ms_per_keyframe"]},
-            "python_host_loop_on_gpu": py, "cpu_baseline": cpu, "host": host_info(),
-        }
+                "python_host_loop_on_gpu": py, "cpu_baseline": cpu})
     return out
 
 
@@ -1127,16 +1244,18 @@ def run_batch(a, rank, world, local, dist):
     for i in range(max(a.warmup // 4, 2)):
         step(i)
     sync()
-    # per-stage GPU time of one launch (library event brackets; untimed)
-    lib.orbmi_set_profiling(ex.handle, 0x1FF)
-    reset_profile(ex.handle)
-    for i in range(4):
-        step(i)
-    sync()
-    st_ms, st_n = read_profile(ex.handle)
-    lib.orbmi_set_profiling(ex.handle, 0)
-    stage_ms = {_capi.STAGES[s]: round(st_ms[s] / 4, 5) for s in range(_capi.NUM_STAGES)
-                if st_n[s] and s < len(_capi.STAGES)}
+    stage_ms = None
+    if a.full:
+        # per-stage GPU time of one launch (library event brackets; untimed)
+        lib.orbmi_set_profiling(ex.handle, 0x1FF)
+        reset_profile(ex.handle)
+        for i in range(4):
+            step(i)
+        sync()
+        st_ms, st_n = read_profile(ex.handle)
+        lib.orbmi_set_profiling(ex.handle, 0)
+        stage_ms = {_capi.STAGES[s]: round(st_ms[s] / 4, 5) for s in range(_capi.NUM_STAGES)
+                    if st_n[s] and s < len(_capi.STAGES)}
     steps = max(a.steps // 10, 5)
     if dist:
         dist.barrier()
@@ -1152,11 +1271,18 @@ def run_batch(a, rank, world, local, dist):
     W, H = level_geometry(rows, cols)
     P = sum(w * h for w, h in zip(W, H))
     B = (7 * P + 60 * kp) * nb
+    if a.dump_outputs and rank == 0:  # every frame's count, the first 16 frames' keypoints and descriptors
+        n = cnt.cpu().numpy()
+        k, d = kps[:16].cpu().numpy(), desc[:16].cpu().numpy()
+        live = np.arange(cap)[None, :] < n[:16, None]  # rows past a frame's count are not outputs
+        dump_outputs(a.dump_outputs, {
+            "counts": n, "keypoints": np.where(live[..., None], keypoints_f32(k).reshape(k.shape), np.float32(0)),
+            "descriptors": np.where(live[..., None], d, np.uint8(0))})
     out = None
     if rank == 0:
         cpu = None
         cpu_tp = None
-        if not a.no_cpu_baseline and world == 1:
+        if a.full and not a.no_cpu_baseline and world == 1:
             O = oracle_native()
             p = O.params(5000)
             n, t0 = 0, time.perf_counter()

@@ -689,6 +689,20 @@ class LocalMapper:
                                                            b["feat"][:kf.n].cpu().numpy()))
         return out
 
+    def last_job_outputs(self):
+        """What the last finished LocalMappingJob's searches found, read back (call after wait()):
+        tri[nnb, n] = SearchForTriangulation's match per neighbour and keypoint (-1: none),
+        tri_ok[nnb, n] = the pairs CreateNewMapPoints accepted, x3d[nnb, n, 3] = their points
+        (zero where not accepted), fuse_match = the Fuse searches' best keypoint per candidate
+        (every target's, then the keyframe's own; -1: none).  None before the first job."""
+        o = self._out
+        if o is None:
+            return None
+        self._ms.synchronize()
+        ok = o["tri_ok"]().astype(bool)
+        return {"tri": o["tri"](), "tri_ok": ok, "x3d": np.where(ok[..., None], o["x3d"](), np.float32(0)),
+                "fuse_match": o["bi"][:o["n_fuse"]].cpu().numpy()}
+
     def _on_ba_enqueued(self, _arg):
         """LocalBA's enqueued hook (orbmi_ba_set_enqueued_hook): the next queued keyframe's
         ComputeBoW, beside the solve.  Never raises into the C caller (errors surface in wait())."""

@@ -94,12 +94,13 @@ def test_write_then_load_kitti_synthetic(tmp_path):
     assert abs(float(s.th_depth) - 386.1448 * 35 / 718.856) < 1e-4
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/Examples"), reason="reference tree not present")
 @pytest.mark.parametrize("rel,nfeat,fps", [("Examples/Stereo/KITTI00-02.yaml", 2000, 10),
                                            ("Examples/Stereo/EuRoC.yaml", 1200, 20),
                                            ("Examples/RGB-D/TUM1.yaml", 1000, 30)])
 def test_reference_settings_files(rel, nfeat, fps):
-    """The reference's own settings files (read as data) parse with the values they state."""
-    s = load_settings(os.path.join("/root/reference", rel))
+    """The reference's own settings files (read as data; copies under tests/golden/settings/)
+    parse with the values they state."""
+    golden = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "settings")
+    s = load_settings(os.path.join(golden, os.path.basename(rel)))
     assert s.n_features == nfeat and s.max_frames == fps and s.n_levels == 8
     assert s.ini_th_fast == 20 and s.min_th_fast == 7

@@ -130,7 +130,7 @@ def test_bench_config4_gloo_two_ranks(tmp_path):
     env = dict(os.environ)
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--mode", "track", "--gpus", "2", "--dist-backend", "gloo",
-           "--steps", "12", "--warmup", "4", "--frames", "4", "--no-cpu-baseline"]
+           "--steps", "12", "--warmup", "4", "--frames", "4", "--full", "--no-cpu-baseline"]
     p = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stdout[-3000:] + p.stderr[-3000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]

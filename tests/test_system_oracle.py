@@ -15,9 +15,12 @@ NFRAMES = 6
 
 
 @functools.lru_cache(maxsize=None)
-def _run(tmpdir="/tmp/orbmi_sys_oracle", n=NFRAMES):
-    import os
-    os.makedirs(tmpdir, exist_ok=True)
+def _run(n=NFRAMES):
+    import atexit
+    import shutil
+    import tempfile
+    tmpdir = tempfile.mkdtemp(prefix="orbmi_sys_oracle_")  # (cached for the session: removed at exit)
+    atexit.register(shutil.rmtree, tmpdir, ignore_errors=True)
     s = sequence_settings(tmpdir)
     be = OracleBackend(s, small_vocabulary())
     slam = StereoSLAM(s, backend=be)

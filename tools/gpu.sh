@@ -9,10 +9,10 @@
 #   tests            pytest -m gpu (whole suite)
 #   tests=EXPR       pytest -m gpu -k EXPR
 #   smoke            __graft_entry__.smoke()
-#   bench            bench.py (default track mode, with the CPU baseline)
-#   bench_quick      bench.py --steps 60 --warmup 8 --no-cpu-baseline
-#   bench_MODE       bench.py --mode MODE (lba, batch, extract, system)
-#   gloo2            bench.py --gpus 2 --dist-backend gloo (config 4 rehearsal on one device)
+#   bench            bench.py --full (default track mode, every profile and the CPU baseline)
+#   bench_quick      bench.py --steps 60 --warmup 8 (the headline figure alone)
+#   bench_MODE       bench.py --full --mode MODE (lba, batch, extract, system)
+#   gloo2            bench.py --full --gpus 2 --dist-backend gloo (config 4 rehearsal on one device)
 #   prof             rocprofv3 --kernel-trace --stats of the default bench
 #   prof_MODE        the same for --mode MODE
 #   proflib=LIB      the default bench's kernel stats on another library build
@@ -75,18 +75,18 @@ for step in "$@"; do
         smoke)
             run smoke 300 python -c "import __graft_entry__ as g; g.smoke()"; cat $OUT/smoke.log;;
         bench)
-            run bench 500 python bench.py; tail -1 $OUT/bench.log | tee $P/bench.json;;
+            run bench 500 python bench.py --full; tail -1 $OUT/bench.log | tee $P/bench.json;;
         frame_events)
             # which chain ends the headline's timed region (tracking_done_ms / mapping_done_ms)
             run frame_events 500 python bench.py --frame-events --steps 200 --warmup 10 --no-cpu-baseline
             tail -1 $OUT/frame_events.log | tee $P/bench_frame_events.json;;
         bench_quick)
-            run bench_quick 300 python bench.py --steps 60 --warmup 8 --no-cpu-baseline; tail -1 $OUT/bench_quick.log;;
+            run bench_quick 300 python bench.py --steps 60 --warmup 8; tail -1 $OUT/bench_quick.log;;
         bench_*)
             m=${step#bench_}
-            run bench_$m 500 python bench.py $(modeargs $m); tail -1 $OUT/bench_$m.log | tee $P/bench_$m.json;;
+            run bench_$m 500 python bench.py --full $(modeargs $m); tail -1 $OUT/bench_$m.log | tee $P/bench_$m.json;;
         gloo2)
-            run gloo2 500 python bench.py --gpus 2 --dist-backend gloo --steps 40 --warmup 8 --no-cpu-baseline
+            run gloo2 500 python bench.py --full --gpus 2 --dist-backend gloo --steps 40 --warmup 8 --no-cpu-baseline
             tail -1 $OUT/gloo2.log | tee $P/bench_config4_gloo2.json;;
         hiptrace)
             # kernel trace + HIP API trace of a short default bench (host enqueue vs GPU timeline)
@@ -170,8 +170,8 @@ for step in "$@"; do
             # default bench with / without an environment knob (VAR=VALUE), 3 alternations
             kv=${step#envab=}
             for i in 1 2 3; do
-                run envab_A$i 300 python bench.py --steps 100 --warmup 10 --no-cpu-baseline
-                run envab_B$i 300 env $kv python bench.py --steps 100 --warmup 10 --no-cpu-baseline
+                run envab_A$i 300 python bench.py --full --steps 100 --warmup 10 --no-cpu-baseline
+                run envab_B$i 300 env $kv python bench.py --full --steps 100 --warmup 10 --no-cpu-baseline
                 echo "default $(tail -1 $OUT/envab_A$i.log | python -c 'import json,sys; d=json.load(sys.stdin); print(d["value"], d.get("pcie_inclusive", {}).get("value"), d["phase_ms_per_frame"])')  $kv $(tail -1 $OUT/envab_B$i.log | python -c 'import json,sys; d=json.load(sys.stdin); print(d["value"], d.get("pcie_inclusive", {}).get("value"), d["phase_ms_per_frame"])')" | tee -a $OUT/envab.txt
             done;;
         envbatch=*)
@@ -179,16 +179,16 @@ for step in "$@"; do
             kv=${step#envbatch=}
             v() { tail -1 $OUT/$1.log | python -c 'import json,sys; d=json.load(sys.stdin); print(d["value"], d.get("stage_ms_per_launch"))'; }
             for i in 1 2 3; do
-                run envb_A$i 300 python bench.py --mode batch --steps 50 --warmup 4 --no-cpu-baseline
-                run envb_B$i 300 env $kv python bench.py --mode batch --steps 50 --warmup 4 --no-cpu-baseline
+                run envb_A$i 300 python bench.py --full --mode batch --steps 50 --warmup 4 --no-cpu-baseline
+                run envb_B$i 300 env $kv python bench.py --full --mode batch --steps 50 --warmup 4 --no-cpu-baseline
                 echo "default $(v envb_A$i) | $kv $(v envb_B$i)" | tee -a $OUT/envbatch.txt
             done;;
         abbatch=*)
             # config-5 (batch mode) A/B of two library builds, 3 alternations, stage times kept
             pair=${step#abbatch=}; A=${pair%,*}; B=${pair#*,}
             for i in 1 2 3; do
-                ORBMI_LIB=$A run abb_A$i 300 python bench.py --mode batch --steps 50 --warmup 4 --no-cpu-baseline
-                ORBMI_LIB=$B run abb_B$i 300 python bench.py --mode batch --steps 50 --warmup 4 --no-cpu-baseline
+                ORBMI_LIB=$A run abb_A$i 300 python bench.py --full --mode batch --steps 50 --warmup 4 --no-cpu-baseline
+                ORBMI_LIB=$B run abb_B$i 300 python bench.py --full --mode batch --steps 50 --warmup 4 --no-cpu-baseline
                 echo "A $(tail -1 $OUT/abb_A$i.log | python -c 'import json,sys; d=json.load(sys.stdin); print(d["value"], d.get("stage_ms_per_launch") or d.get("stage_ms_per_step"))')  B $(tail -1 $OUT/abb_B$i.log | python -c 'import json,sys; d=json.load(sys.stdin); print(d["value"], d.get("stage_ms_per_launch") or d.get("stage_ms_per_step"))')" | tee -a $OUT/abbatch.txt
             done;;
         ab=*)
@@ -205,7 +205,7 @@ for step in "$@"; do
             for i in 1 2 3; do
                 for l in ${libs//,/ }; do
                     n=$(basename $l .so)
-                    ORBMI_LIB=$l run absys_${n}_$i 300 python bench.py --mode system --no-cpu-baseline
+                    ORBMI_LIB=$l run absys_${n}_$i 300 python bench.py --full --mode system --no-cpu-baseline
                     echo "$n $(tail -1 $OUT/absys_${n}_$i.log | python -c 'import json,sys; d=json.load(sys.stdin); print(d["value"], d["ate_rmse_m"], d["phase_ms_per_frame"]["total"], d["local_mapping_ms_per_keyframe"], d["synchronous_local_mapping"]["frames_per_s"])')" | tee -a $OUT/absys.txt
                 done
             done;;
@@ -298,8 +298,8 @@ for step in "$@"; do
             # wave (ORBMI_DESC=wave), 2 alternations
             v() { tail -1 $OUT/$1.log | python -c 'import json,sys; d=json.load(sys.stdin); print(d["value"], d["stage_ms_per_launch"])'; }
             for i in 1 2; do
-                run descab_4_$i 300 python bench.py --mode batch --steps 20 --warmup 4 --no-cpu-baseline
-                ORBMI_DESC=wave run descab_w_$i 300 python bench.py --mode batch --steps 20 --warmup 4 --no-cpu-baseline
+                run descab_4_$i 300 python bench.py --full --mode batch --steps 20 --warmup 4 --no-cpu-baseline
+                ORBMI_DESC=wave run descab_w_$i 300 python bench.py --full --mode batch --steps 20 --warmup 4 --no-cpu-baseline
                 echo "4/wave: $(v descab_4_$i) | 1/wave: $(v descab_w_$i)" | tee -a $OUT/descab.txt
             done; cp $OUT/descab.txt $P/;;
         octtrace)
@@ -319,8 +319,8 @@ for step in "$@"; do
             # segment-test and score stages (ORBMI_FAST=split), 3 alternations
             v() { tail -1 $OUT/$1.log | python -c 'import json,sys; d=json.load(sys.stdin); print(d["value"], d["stage_ms_per_launch"]["fast"])'; }
             for i in 1 2 3; do
-                run fastab_s_$i 300 python bench.py --mode batch --steps 20 --warmup 4 --no-cpu-baseline
-                ORBMI_FAST=split run fastab_p_$i 300 python bench.py --mode batch --steps 20 --warmup 4 --no-cpu-baseline
+                run fastab_s_$i 300 python bench.py --full --mode batch --steps 20 --warmup 4 --no-cpu-baseline
+                ORBMI_FAST=split run fastab_p_$i 300 python bench.py --full --mode batch --steps 20 --warmup 4 --no-cpu-baseline
                 echo "one pass: $(v fastab_s_$i) | split: $(v fastab_p_$i)" | tee -a $OUT/fastab.txt
             done; cp $OUT/fastab.txt $P/;;
         fastseg)
@@ -329,10 +329,10 @@ for step in "$@"; do
             v() { tail -1 $OUT/$1.log | python -c 'import json,sys; d=json.load(sys.stdin); print(d["value"], d["stage_ms_per_launch"]["fast"])'; }
             for i in 1 2; do
                 for sg in 0 1 2; do
-                    ORBMI_FAST_SEG=$sg run fastseg_${sg}_$i 300 python bench.py --mode batch --steps 20 --warmup 4 --no-cpu-baseline
+                    ORBMI_FAST_SEG=$sg run fastseg_${sg}_$i 300 python bench.py --full --mode batch --steps 20 --warmup 4 --no-cpu-baseline
                     echo "seg $sg: $(v fastseg_${sg}_$i)" | tee -a $OUT/fastseg.txt
                 done
-                ORBMI_FAST=v1 run fastseg_v1_$i 300 python bench.py --mode batch --steps 20 --warmup 4 --no-cpu-baseline
+                ORBMI_FAST=v1 run fastseg_v1_$i 300 python bench.py --full --mode batch --steps 20 --warmup 4 --no-cpu-baseline
                 echo "v1: $(v fastseg_v1_$i)" | tee -a $OUT/fastseg.txt
             done; cp $OUT/fastseg.txt $P/;;
         blurab)
