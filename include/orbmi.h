@@ -108,6 +108,54 @@ int orbmi_compute_stereo_matches(orbmi_extractor* left, int item_left, orbmi_ext
 int orbmi_compute_stereo_matches_batch_device(orbmi_extractor* h, float bf, float fx,
                                               float* d_u_right, float* d_depth);
 
+/* ---- RGB-D Frame: UndistortKeyPoints, ComputeImageBounds, ComputeStereoFromRGBD ----------- */
+
+/* mK and mDistCoef (src/Tracking.cc:60-80): dist = k1 k2 p1 p2 [k3]; ndist = 4 or 5 (4: k3 = 0).
+ * Undistortion is cv::undistortPoints(pts, pts, mK, mDistCoef, cv::Mat(), mK) restated (OpenCV
+ * 3.x cvUndistortPoints: five fixed iterations in fp64), applied only when
+ * dist[0] != 0 as the reference tests only k1 (src/Frame.cc:437, 473). */
+typedef struct orbmi_camera {
+    float fx, fy, cx, cy;
+    float dist[5];
+    int ndist;
+} orbmi_camera;
+
+#define ORBMI_DEPTH_F32 0          /* CV_32F depth map                                */
+#define ORBMI_DEPTH_U16 1          /* CV_16U depth map (TUM: 5000 units per metre)    */
+
+/* Frame::ComputeImageBounds (src/Frame.cc:471-499) for a rows x cols image: out = mnMinX, mnMaxX,
+ * mnMinY, mnMaxY.  Host only, no GPU. */
+int orbmi_compute_image_bounds(float fx, float fy, float cx, float cy, const float* dist, int ndist, int rows,
+                               int cols, float out[4]);
+
+/* Frame::UndistortKeyPoints + Frame::ComputeStereoFromRGBD (src/Frame.cc:434-469, 678-699) on the
+ * device-resident keypoints of item `item` of the extractor's last extraction, on its stream.
+ * depth: rows x cols depth map (host or device), ORBMI_DEPTH_F32 or ORBMI_DEPTH_U16, row pitch
+ * depth_step_bytes; depth_factor = mDepthMapFactor (already inverted, src/Tracking.cc:143-147):
+ * d = depth[(int)v][(int)u] * factor in float32 (a float32 map with factor 1 is taken as is).
+ * keys_un[i] = the keypoint with pt undistorted (mvKeysUn); d > 0: depth_out[i] = d, u_right[i] =
+ * keys_un[i].x - bf / d; otherwise both -1.  n = capacity of the outputs (host or device,
+ * detected per call): fewer than the item's keypoints -> ORBMI_E_CAP. */
+int orbmi_compute_stereo_from_rgbd(orbmi_extractor* h, int item, const void* depth, int depth_type,
+                                   size_t depth_step_bytes, float depth_factor, int rows, int cols,
+                                   const orbmi_camera* camera, float bf, orbmi_keypoint* keys_un, float* u_right,
+                                   float* depth_out, int n);
+
+/* The same on the caller's n raw keypoints (mvKeys; host or device), without extractor state, on
+ * `device`.  A key whose truncated position (int)v, (int)u lies outside rows x cols gets
+ * depth -1, u_right -1 and is copied unchanged; nothing is read out of bounds. */
+int orbmi_compute_stereo_from_rgbd_keys(int device, const orbmi_keypoint* keys, int n, const void* depth,
+                                        int depth_type, size_t depth_step_bytes, float depth_factor, int rows,
+                                        int cols, const orbmi_camera* camera, float bf, orbmi_keypoint* keys_un,
+                                        float* u_right, float* depth_out);
+
+/* cvtColor(im, gray, CV_RGB2GRAY / CV_BGR2GRAY / CV_RGBA2GRAY / CV_BGRA2GRAY) of
+ * Tracking::GrabImageRGBD (src/Tracking.cc:208-224): interleaved u8 with `channels` = 3 or 4
+ * (alpha ignored), rgb = Camera.RGB (1: R first, 0: B first); gray = (R*4899 + G*9617 + B*1868 +
+ * 8192) >> 14.  image / gray: host or device of `device`, row pitches in bytes. */
+int orbmi_cvt_gray(int device, const uint8_t* image, size_t image_step, int channels, int rgb, int rows, int cols,
+                   uint8_t* gray, size_t gray_step);
+
 /* ---- ORBmatcher ----------------------------------------------------------------------- */
 
 /* Read-only view of the Frame members the matchers use (include/Frame.h).  Pointers may be
@@ -698,6 +746,31 @@ int orbmi_slam_track_stereo(orbmi_slam* h, const uint8_t* left, const uint8_t* r
 int orbmi_slam_track_stereo_ahead(orbmi_slam* h, const uint8_t* left, const uint8_t* right, int rows, int cols,
                                   size_t step, double timestamp, const uint8_t* next_left,
                                   const uint8_t* next_right, float* tcw_out, int* has_pose);
+
+/* System(strSettingsFile, RGBD): what Tracking reads for an RGB-D sensor beyond
+ * orbmi_slam_settings -- mDistCoef (ndist = 4 or 5), mDepthMapFactor already inverted
+ * (src/Tracking.cc:143-147) and mbRGB. */
+typedef struct orbmi_rgbd_settings {
+    float dist[5];
+    int ndist;
+    float depth_map_factor;
+    int rgb;
+} orbmi_rgbd_settings;
+
+/* orbmi_slam_create for the RGB-D sensor: one ORBextractor, the image bounds of the distorted
+ * camera (orbmi_compute_image_bounds) computed once.  Everything after the Frame constructor is the
+ * stereo handle's (the reference takes the same branches for RGBD as for STEREO). */
+int orbmi_slam_create_rgbd(const orbmi_slam_settings* s, const orbmi_rgbd_settings* r, int device,
+                           orbmi_vocabulary* vocabulary, orbmi_slam** out);
+
+/* System::TrackRGBD(im, depthmap, timestamp) (src/System.cc:161-210, Tracking::GrabImageRGBD):
+ * image = host u8 with `channels` 1, 3 or 4 (row pitch image_step bytes), depth = host depth map
+ * (ORBMI_DEPTH_F32 / ORBMI_DEPTH_U16, row pitch depth_step bytes), both rows x cols.  Outputs as
+ * orbmi_slam_track_stereo.  ORBMI_E_STATE on a stereo handle; the stereo calls return
+ * ORBMI_E_STATE on an RGB-D handle. */
+int orbmi_slam_track_rgbd(orbmi_slam* h, const uint8_t* image, int channels, size_t image_step, const void* depth,
+                          int depth_type, size_t depth_step, int rows, int cols, double timestamp, float* tcw_out,
+                          int* has_pose);
 
 /* The counters of the `frame`-th TrackStereo call (0-based; the record stays across a reset,
  * while frame ids restart); ORBMI_E_ARG past the last call. */

@@ -332,6 +332,46 @@ private:
     orbmi_ba* h_ = nullptr;
 };
 
+// ORB_SLAM2::System for the RGB-D sensor (include/System.h:58-83, src/System.cc:161-210) over the
+// native loop (orbmi_slam_create_rgbd / orbmi_slam_track_rgbd).  settings: the Tracking
+// constructor's reads (src/Tracking.cc:53-143); rgbd: mDistCoef, mDepthMapFactor (already
+// inverted) and mbRGB.  The vocabulary is borrowed.
+class System {
+public:
+    System(const orbmi_slam_settings& settings, const orbmi_rgbd_settings& rgbd, orbmi_vocabulary* vocabulary = nullptr,
+           int device = 0) {
+        check(orbmi_slam_create_rgbd(&settings, &rgbd, device, vocabulary, &h_), "orbmi_slam_create_rgbd");
+    }
+    ~System() { orbmi_slam_destroy(h_); }
+    System(const System&) = delete;
+    System& operator=(const System&) = delete;
+
+    // cv::Mat System::TrackRGBD(const cv::Mat& im, const cv::Mat& depthmap, const double& timestamp):
+    // im = u8 with 1, 3 or 4 channels (im.data, im.channels(), im.step), depthmap = CV_32F
+    // (ORBMI_DEPTH_F32) or CV_16U (ORBMI_DEPTH_U16) with its step in bytes.  Returns false while
+    // not initialised / lost (the reference's empty Tcw); Tcw = 16 floats, row-major.
+    bool TrackRGBD(const uint8_t* im, int channels, size_t imStep, const void* depthmap, int depthType, size_t depthStep,
+                   int rows, int cols, double timestamp, float* Tcw) {
+        int has = 0;
+        check(orbmi_slam_track_rgbd(h_, im, channels, imStep, depthmap, depthType, depthStep, rows, cols, timestamp, Tcw,
+                                    &has),
+              "orbmi_slam_track_rgbd");
+        return has != 0;
+    }
+
+    void SaveTrajectoryTUM(const std::string& filename) {
+        check(orbmi_slam_save_trajectory_tum(h_, filename.c_str()), "orbmi_slam_save_trajectory_tum");
+    }
+    void SaveKeyFrameTrajectoryTUM(const std::string& filename) {
+        check(orbmi_slam_save_keyframe_trajectory_tum(h_, filename.c_str()), "orbmi_slam_save_keyframe_trajectory_tum");
+    }
+
+    orbmi_slam* handle() const { return h_; }
+
+private:
+    orbmi_slam* h_ = nullptr;
+};
+
 }  // namespace orbmi
 
 #endif  // ORBMI_HPP

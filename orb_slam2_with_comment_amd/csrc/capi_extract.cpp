@@ -213,6 +213,176 @@ int orbmi_compute_stereo_matches_batch_device(orbmi_extractor* h, float bf, floa
 
 }  // extern "C"
 
+// ---- RGB-D Frame stages (rgbd.hip) -----------------------------------------------------
+#include "rgbd.h"
+
+namespace {
+
+bool rgbd_on_device(const void* p) {
+    if (!p) return false;
+    hipPointerAttribute_t at;
+    if (hipPointerGetAttributes(&at, p) != hipSuccess) {
+        (void)hipGetLastError();
+        return false;
+    }
+    return at.type == hipMemoryTypeDevice || at.type == hipMemoryTypeManaged;
+}
+
+// Device buffers of one operator call, freed when it returns (the operator forms synchronise).
+struct RgbdScratch {
+    std::vector<void*> bufs;
+    ~RgbdScratch() {
+        for (void* p : bufs) (void)hipFree(p);
+    }
+    void* take(size_t bytes) {
+        void* p = nullptr;
+        if (hipMalloc(&p, bytes ? bytes : 1) != hipSuccess) return nullptr;
+        bufs.push_back(p);
+        return p;
+    }
+};
+
+// a stream for the operator forms that have no handle
+struct RgbdStream {
+    hipStream_t s = nullptr;
+    ~RgbdStream() {
+        if (s) (void)hipStreamDestroy(s);
+    }
+};
+
+bool rgbd_camera(const orbmi_camera* c, orbmi::UndistortCam* out) {
+    if (!c || (c->ndist != 4 && c->ndist != 5) || c->fx == 0.f || c->fy == 0.f) return false;
+    out->fx = c->fx; out->fy = c->fy; out->cx = c->cx; out->cy = c->cy;
+    for (int k = 0; k < 5; k++) out->dist[k] = k < c->ndist ? c->dist[k] : 0.f;
+    return true;
+}
+
+bool rgbd_depth_ok(const void* depth, int type, size_t step, int rows, int cols) {
+    if (!depth || rows <= 0 || cols <= 0 || (type != ORBMI_DEPTH_F32 && type != ORBMI_DEPTH_U16)) return false;
+    const size_t es = type == ORBMI_DEPTH_U16 ? 2 : 4;
+    return step >= (size_t)cols * es && step % es == 0 && (uintptr_t)depth % es == 0;
+}
+
+// UndistortKeyPoints + ComputeStereoFromRGBD of nk device keypoints into host or device outputs
+int rgbd_operator(hipStream_t stream, const orbmi_keypoint* d_keys, int nk, const void* depth, int depth_type,
+                  size_t depth_step, float factor, int rows, int cols, const orbmi::UndistortCam& cam, float bf,
+                  orbmi_keypoint* keys_un, float* u_right, float* depth_out) {
+    if (nk <= 0) return ORBMI_OK;
+    RgbdScratch scratch;
+    const void* d_depth = depth;
+    if (!rgbd_on_device(depth)) {
+        // (the last row ends with its pixels: a view into a larger array owns no pitch padding there)
+        const size_t bytes = (size_t)(rows - 1) * depth_step + (size_t)cols * (depth_type == ORBMI_DEPTH_U16 ? 2 : 4);
+        void* d = scratch.take(bytes);
+        if (!d) return ORBMI_E_HIP;
+        ORBMI_HIP(hipMemcpyAsync(d, depth, bytes, hipMemcpyHostToDevice, stream));
+        d_depth = d;
+    }
+    const bool kd = rgbd_on_device(keys_un), ud = rgbd_on_device(u_right), dd = rgbd_on_device(depth_out);
+    orbmi_keypoint* d_un = kd ? keys_un : (orbmi_keypoint*)scratch.take((size_t)nk * sizeof(orbmi_keypoint));
+    float* d_ur = ud ? u_right : (float*)scratch.take((size_t)nk * sizeof(float));
+    float* d_dep = dd ? depth_out : (float*)scratch.take((size_t)nk * sizeof(float));
+    if (!d_un || !d_ur || !d_dep) return ORBMI_E_HIP;
+    int rc = orbmi::rgbd_frame_run(stream, d_keys, nullptr, nk, d_depth, depth_type, depth_step, factor, rows, cols,
+                                   cam, bf, d_un, d_ur, d_dep);
+    if (rc) return rc;
+    if (!kd) ORBMI_HIP(hipMemcpyAsync(keys_un, d_un, (size_t)nk * sizeof(orbmi_keypoint), hipMemcpyDeviceToHost, stream));
+    if (!ud) ORBMI_HIP(hipMemcpyAsync(u_right, d_ur, (size_t)nk * sizeof(float), hipMemcpyDeviceToHost, stream));
+    if (!dd) ORBMI_HIP(hipMemcpyAsync(depth_out, d_dep, (size_t)nk * sizeof(float), hipMemcpyDeviceToHost, stream));
+    ORBMI_HIP(hipStreamSynchronize(stream));  // the scratch is freed on return
+    return ORBMI_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int orbmi_compute_image_bounds(float fx, float fy, float cx, float cy, const float* dist, int ndist, int rows,
+                               int cols, float out[4]) {
+    if (!out || rows <= 0 || cols <= 0 || (ndist > 0 && !dist) || ndist < 0 || ndist > 5 || fx == 0.f || fy == 0.f)
+        return ORBMI_E_ARG;
+    orbmi::UndistortCam c{fx, fy, cx, cy, {0.f, 0.f, 0.f, 0.f, 0.f}};
+    for (int k = 0; k < ndist; k++) c.dist[k] = dist[k];
+    orbmi::image_bounds(c, rows, cols, out);
+    return ORBMI_OK;
+}
+
+int orbmi_compute_stereo_from_rgbd(orbmi_extractor* h, int item, const void* depth, int depth_type,
+                                   size_t depth_step_bytes, float depth_factor, int rows, int cols,
+                                   const orbmi_camera* camera, float bf, orbmi_keypoint* keys_un, float* u_right,
+                                   float* depth_out, int n) {
+    orbmi::UndistortCam cam;
+    if (!h || n < 0 || (n > 0 && (!keys_un || !u_right || !depth_out)) || !rgbd_camera(camera, &cam) ||
+        !rgbd_depth_ok(depth, depth_type, depth_step_bytes, rows, cols))
+        return ORBMI_E_ARG;
+    Extractor& e = h->ex;
+    if (e.levels.empty() || item < 0 || item >= e.last_batch || !e.last_kps || !e.last_counts) return ORBMI_E_STATE;
+    if (rows != e.rows || cols != e.cols) return ORBMI_E_ARG;
+    ORBMI_HIP(hipSetDevice(e.device));
+    int nk = 0;
+    ORBMI_HIP(hipMemcpyAsync(&nk, e.last_counts + item, sizeof(int), hipMemcpyDeviceToHost, e.stream));
+    ORBMI_HIP(hipStreamSynchronize(e.stream));
+    nk = std::min(nk, e.last_capacity);
+    if (n < nk) return ORBMI_E_CAP;
+    return rgbd_operator(e.stream, e.last_kps + (size_t)item * e.last_capacity, nk, depth, depth_type,
+                         depth_step_bytes, depth_factor, rows, cols, cam, bf, keys_un, u_right, depth_out);
+}
+
+int orbmi_compute_stereo_from_rgbd_keys(int device, const orbmi_keypoint* keys, int n, const void* depth,
+                                        int depth_type, size_t depth_step_bytes, float depth_factor, int rows,
+                                        int cols, const orbmi_camera* camera, float bf, orbmi_keypoint* keys_un,
+                                        float* u_right, float* depth_out) {
+    orbmi::UndistortCam cam;
+    if (n < 0 || (n > 0 && (!keys || !keys_un || !u_right || !depth_out)) || !rgbd_camera(camera, &cam) ||
+        !rgbd_depth_ok(depth, depth_type, depth_step_bytes, rows, cols))
+        return ORBMI_E_ARG;
+    if (n == 0) return ORBMI_OK;
+    ORBMI_HIP(hipSetDevice(device));
+    RgbdStream st;
+    ORBMI_HIP(hipStreamCreateWithFlags(&st.s, hipStreamNonBlocking));
+    RgbdScratch scratch;
+    const orbmi_keypoint* d_keys = keys;
+    if (!rgbd_on_device(keys)) {
+        void* d = scratch.take((size_t)n * sizeof(orbmi_keypoint));
+        if (!d) return ORBMI_E_HIP;
+        ORBMI_HIP(hipMemcpyAsync(d, keys, (size_t)n * sizeof(orbmi_keypoint), hipMemcpyHostToDevice, st.s));
+        d_keys = (const orbmi_keypoint*)d;
+    }
+    return rgbd_operator(st.s, d_keys, n, depth, depth_type, depth_step_bytes, depth_factor, rows, cols, cam, bf,
+                         keys_un, u_right, depth_out);
+}
+
+int orbmi_cvt_gray(int device, const uint8_t* image, size_t image_step, int channels, int rgb, int rows, int cols,
+                   uint8_t* gray, size_t gray_step) {
+    if (!image || !gray || (channels != 3 && channels != 4) || rows <= 0 || cols <= 0 || rows > 65535 ||
+        image_step < (size_t)cols * channels || gray_step < (size_t)cols)
+        return ORBMI_E_ARG;
+    ORBMI_HIP(hipSetDevice(device));
+    RgbdStream st;
+    ORBMI_HIP(hipStreamCreateWithFlags(&st.s, hipStreamNonBlocking));
+    RgbdScratch scratch;
+    const uint8_t* d_src = image;
+    size_t src_step = image_step;
+    if (!rgbd_on_device(image)) {
+        src_step = (size_t)cols * channels;
+        uint8_t* d = (uint8_t*)scratch.take((size_t)rows * src_step);
+        if (!d) return ORBMI_E_HIP;
+        ORBMI_HIP(hipMemcpy2DAsync(d, src_step, image, image_step, src_step, rows, hipMemcpyHostToDevice, st.s));
+        d_src = d;
+    }
+    const bool gd = rgbd_on_device(gray);
+    uint8_t* d_dst = gd ? gray : (uint8_t*)scratch.take((size_t)rows * cols);
+    if (!d_dst) return ORBMI_E_HIP;
+    const int rc = orbmi::cvt_gray_run(st.s, d_src, src_step, channels, rgb ? 1 : 0, rows, cols, d_dst,
+                                       gd ? gray_step : (size_t)cols);
+    if (rc) return rc;
+    if (!gd) ORBMI_HIP(hipMemcpy2DAsync(gray, gray_step, d_dst, cols, cols, rows, hipMemcpyDeviceToHost, st.s));
+    ORBMI_HIP(hipStreamSynchronize(st.s));
+    return ORBMI_OK;
+}
+
+}  // extern "C"
+
 extern "C" int orbmi_set_profiling(orbmi_extractor* h, unsigned stage_mask) {
     if (!h) return ORBMI_E_ARG;
     h->ex.prof_mask = stage_mask;

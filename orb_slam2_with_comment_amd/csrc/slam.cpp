@@ -2,6 +2,8 @@
 // synchronous LocalMapping around the MI355X operators of this library (include/orbmi.h).
 //
 //   System::TrackStereo        -> orbmi_slam_track_stereo         src/System.cc:110-159
+//   System::TrackRGBD          -> orbmi_slam_track_rgbd           src/System.cc:161-210
+//   Frame::Frame (RGB-D)       -> Slam::frame_rgbd                src/Frame.cc:119-171
 //   Tracking::Track (stereo)   -> Slam::track                     src/Tracking.cc:287-581
 //   StereoInitialization       -> Slam::stereo_initialization     src/Tracking.cc:584-636
 //   TrackReferenceKeyFrame     -> Slam::track_reference_kf        src/Tracking.cc:871-917
@@ -43,6 +45,7 @@
 
 #include "../../include/orbmi.h"
 #include "../../include/orbmi_debug.h"
+#include "rgbd.h"
 #include "tri_geom.h"
 
 namespace {
@@ -269,6 +272,14 @@ thread_local bool on_mapping_thread = false;
 
 struct orbmi_slam {
     orbmi_slam_settings s{};
+    // System(..., RGBD): mDistCoef / mDepthMapFactor / mbRGB, the camera as the undistortion takes
+    // it, and the device copy of the frame's image and depth map
+    bool rgbd = false;
+    orbmi_rgbd_settings rs{};
+    orbmi::UndistortCam ucam{};
+    // mnMinX, mnMaxX, mnMinY, mnMaxY (Frame::ComputeImageBounds, src/Frame.cc:471-499), computed
+    // once at creation as the reference does for its first Frame (mbInitialComputations)
+    float bounds[4] = {0.f, 0.f, 0.f, 0.f};
     int device = 0;
     orbmi_extractor* left = nullptr;
     orbmi_extractor* right = nullptr;
@@ -617,9 +628,9 @@ struct orbmi_slam {
         v.tcw = tcw;
         v.fx = s.fx; v.fy = s.fy; v.cx = s.cx; v.cy = s.cy; v.bf = s.bf;
         v.mb = s.bf / s.fx;
-        v.min_x = 0.f; v.max_x = (float)s.width; v.min_y = 0.f; v.max_y = (float)s.height;  // no distortion
-        v.grid_w_inv = 64.f / (float)s.width;
-        v.grid_h_inv = 48.f / (float)s.height;
+        v.min_x = bounds[0]; v.max_x = bounds[1]; v.min_y = bounds[2]; v.max_y = bounds[3];
+        v.grid_w_inv = 64.f / (bounds[1] - bounds[0]);  // (src/Frame.cc:101-102, 155-156)
+        v.grid_h_inv = 48.f / (bounds[3] - bounds[2]);
         v.nlevels = (int)scale_factors.size();
         v.scale_factors = scale_factors.data();
         v.log_scale_factor = log_scale_factor;
@@ -645,6 +656,28 @@ struct orbmi_slam {
             if (k != a && k != b) return k;
         return -1;
     }
+    // the device slots and the pinned read-back buffers, on first use
+    int ensure_slots() {
+        if (dev.kps[0]) return ORBMI_OK;
+        const int cap = s.n_features + 16 * s.n_levels + 64;
+        dev.cap = cap;
+        for (int k = 0; k < kSlots; k++) {
+            if (hipMalloc((void**)&dev.kps[k], 2 * (size_t)cap * sizeof(orbmi_keypoint)) != hipSuccess ||
+                hipMalloc((void**)&dev.desc[k], 2 * (size_t)cap * 32) != hipSuccess ||
+                hipMalloc((void**)&dev.cnt[k], 2 * sizeof(int)) != hipSuccess ||
+                hipMalloc((void**)&dev.ur[k], 2 * (size_t)cap * sizeof(float)) != hipSuccess ||
+                hipMalloc((void**)&dev.dep[k], 2 * (size_t)cap * sizeof(float)) != hipSuccess)
+                return ORBMI_E_HIP;
+        }
+        if (hipHostMalloc((void**)&dev.h_kps, (size_t)cap * sizeof(orbmi_keypoint), hipHostMallocDefault) != hipSuccess ||
+            hipHostMalloc((void**)&dev.h_desc, (size_t)cap * 32, hipHostMallocDefault) != hipSuccess ||
+            hipHostMalloc((void**)&dev.h_cnt, 2 * sizeof(int), hipHostMallocDefault) != hipSuccess ||
+            hipHostMalloc((void**)&dev.h_ur, (size_t)cap * sizeof(float), hipHostMallocDefault) != hipSuccess ||
+            hipHostMalloc((void**)&dev.h_dep, (size_t)cap * sizeof(float), hipHostMallocDefault) != hipSuccess)
+            return ORBMI_E_HIP;
+        return ORBMI_OK;
+    }
+
     int frame_enqueue(const uint8_t* L, const uint8_t* R, int rows, int cols, size_t step, int k) {
         if (k < 0 || k >= kSlots) return ORBMI_E_ARG;
         const size_t img = (size_t)rows * cols;
@@ -657,24 +690,7 @@ struct orbmi_slam {
             if (hipHostMalloc((void**)&dev.h_img, 2 * img, hipHostMallocDefault) != hipSuccess) return ORBMI_E_HIP;
             dev.img_bytes = 2 * img;
         }
-        if (!dev.kps[0]) {
-            const int cap = s.n_features + 16 * s.n_levels + 64;
-            dev.cap = cap;
-            for (int k = 0; k < kSlots; k++) {
-                if (hipMalloc((void**)&dev.kps[k], 2 * (size_t)cap * sizeof(orbmi_keypoint)) != hipSuccess ||
-                    hipMalloc((void**)&dev.desc[k], 2 * (size_t)cap * 32) != hipSuccess ||
-                    hipMalloc((void**)&dev.cnt[k], 2 * sizeof(int)) != hipSuccess ||
-                    hipMalloc((void**)&dev.ur[k], 2 * (size_t)cap * sizeof(float)) != hipSuccess ||
-                    hipMalloc((void**)&dev.dep[k], 2 * (size_t)cap * sizeof(float)) != hipSuccess)
-                    return ORBMI_E_HIP;
-            }
-            if (hipHostMalloc((void**)&dev.h_kps, (size_t)cap * sizeof(orbmi_keypoint), hipHostMallocDefault) != hipSuccess ||
-                hipHostMalloc((void**)&dev.h_desc, (size_t)cap * 32, hipHostMallocDefault) != hipSuccess ||
-                hipHostMalloc((void**)&dev.h_cnt, 2 * sizeof(int), hipHostMallocDefault) != hipSuccess ||
-                hipHostMalloc((void**)&dev.h_ur, (size_t)cap * sizeof(float), hipHostMallocDefault) != hipSuccess ||
-                hipHostMalloc((void**)&dev.h_dep, (size_t)cap * sizeof(float), hipHostMallocDefault) != hipSuccess)
-                return ORBMI_E_HIP;
-        }
+        SLAM_CHECK(ensure_slots());
         for (int r = 0; r < rows; r++) {
             std::memcpy(dev.h_img + (size_t)r * cols, L + (size_t)r * step, cols);
             std::memcpy(dev.h_img + img + (size_t)r * cols, R + (size_t)r * step, cols);
@@ -723,6 +739,58 @@ struct orbmi_slam {
         const int slot = free_slot(last_frame.dslot, -1);
         SLAM_CHECK(frame_enqueue(L, R, rows, cols, step, slot));
         return frame_collect(cf, slot);
+    }
+
+    // Frame::Frame (RGB-D, src/Frame.cc:119-171) behind Tracking::GrabImageRGBD's conversions
+    // (src/Tracking.cc:208-230): the image and the depth map go up once (pinned staging: gray or
+    // colour image, then the depth rows), cvtColor when the image has channels, ORBextractor as a
+    // batch of one, UndistortKeyPoints + ComputeStereoFromRGBD in place on the slot's keypoints
+    // (the slot then holds mvKeysUn, all Tracking reads), and the read-back of frame_enqueue --
+    // all on the extractor's stream.
+    int frame_rgbd(TrackedFrame& cf, const uint8_t* image, int channels, size_t image_step, const void* depth,
+                   int depth_type, size_t depth_step, int rows, int cols) {
+        const size_t img = (size_t)rows * cols, es = depth_type == ORBMI_DEPTH_U16 ? 2 : 4;
+        const size_t in_img = img * channels, in_depth = (in_img + 15) & ~(size_t)15, in_bytes = in_depth + img * es;
+        // dev.img: [gray | staged input (image, depth)]; dev.h_img mirrors the staged input
+        const size_t o_in = (img + 255) & ~(size_t)255;
+        if (o_in + in_bytes > dev.img_bytes) {
+            if (dev.img) (void)hipFree(dev.img);
+            if (dev.h_img) (void)hipHostFree(dev.h_img);
+            dev.img = nullptr;
+            dev.h_img = nullptr;
+            dev.img_bytes = 0;
+            if (hipMalloc((void**)&dev.img, o_in + in_bytes) != hipSuccess) return ORBMI_E_HIP;
+            if (hipHostMalloc((void**)&dev.h_img, o_in + in_bytes, hipHostMallocDefault) != hipSuccess) return ORBMI_E_HIP;
+            dev.img_bytes = o_in + in_bytes;
+        }
+        SLAM_CHECK(ensure_slots());
+        const int k = free_slot(last_frame.dslot, -1);  // the last frame's slot is read by this frame's tracking
+        const size_t row_bytes = (size_t)cols * channels;
+        for (int r = 0; r < rows; r++) {
+            std::memcpy(dev.h_img + (size_t)r * row_bytes, image + (size_t)r * image_step, row_bytes);
+            std::memcpy(dev.h_img + in_depth + (size_t)r * cols * es, (const uint8_t*)depth + (size_t)r * depth_step,
+                        (size_t)cols * es);
+        }
+        uint8_t* d_in = dev.img + o_in;
+        if (hipMemcpyAsync(d_in, dev.h_img, in_bytes, hipMemcpyHostToDevice, xstream) != hipSuccess) return ORBMI_E_HIP;
+        const uint8_t* d_gray = d_in;
+        if (channels > 1) {
+            SLAM_CHECK(orbmi::cvt_gray_run(xstream, d_in, row_bytes, channels, rs.rgb ? 1 : 0, rows, cols, dev.img, cols));
+            d_gray = dev.img;
+        }
+        const int cap = dev.cap;
+        SLAM_CHECK(orbmi_extract_batch_device(left, d_gray, 1, rows, cols, cols, img, dev.kps[k], dev.desc[k], dev.cnt[k],
+                                              cap));
+        SLAM_CHECK(orbmi::rgbd_frame_run(xstream, dev.kps[k], dev.cnt[k], cap, d_in + in_depth, depth_type, cols * es,
+                                         rs.depth_map_factor, rows, cols, ucam, s.bf, dev.kps[k], dev.ur[k], dev.dep[k]));
+        if (hipMemcpyAsync(dev.h_cnt, dev.cnt[k], sizeof(int), hipMemcpyDeviceToHost, xstream) != hipSuccess ||
+            hipMemcpyAsync(dev.h_kps, dev.kps[k], (size_t)cap * sizeof(orbmi_keypoint), hipMemcpyDeviceToHost, xstream) !=
+                hipSuccess ||
+            hipMemcpyAsync(dev.h_desc, dev.desc[k], (size_t)cap * 32, hipMemcpyDeviceToHost, xstream) != hipSuccess ||
+            hipMemcpyAsync(dev.h_ur, dev.ur[k], (size_t)cap * sizeof(float), hipMemcpyDeviceToHost, xstream) != hipSuccess ||
+            hipMemcpyAsync(dev.h_dep, dev.dep[k], (size_t)cap * sizeof(float), hipMemcpyDeviceToHost, xstream) != hipSuccess)
+            return ORBMI_E_HIP;
+        return frame_collect(cf, k);
     }
 
     // orbmi_slam_track_stereo_ahead: the Frame constructor of this pair from the extraction
@@ -2784,21 +2852,30 @@ struct orbmi_slam {
 // CUs LocalMapping's stream leaves to Tracking (ORBMI_LM_RESERVE_CUS overrides)
 constexpr int kLmReserveCus = 0;
 
-extern "C" {
-
-int orbmi_slam_create(const orbmi_slam_settings* s, int device, orbmi_vocabulary* vocabulary, orbmi_slam** out) {
+// r: the RGB-D sensor's settings, NULL for the stereo sensor
+static int slam_create(const orbmi_slam_settings* s, const orbmi_rgbd_settings* r, int device,
+                       orbmi_vocabulary* vocabulary, orbmi_slam** out) {
     if (!s || !out || s->width <= 0 || s->height <= 0 || s->n_levels < 1 || s->n_levels > 16 || s->fx == 0.f)
         return ORBMI_E_ARG;
+    if (r && ((r->ndist != 4 && r->ndist != 5) || s->fy == 0.f || s->height > 65535)) return ORBMI_E_ARG;
     *out = nullptr;
     orbmi_slam* h = new (std::nothrow) orbmi_slam();
     if (!h) return ORBMI_E_ARG;
     h->s = *s;
     h->device = device;
     h->voc = vocabulary;
+    h->ucam = orbmi::UndistortCam{s->fx, s->fy, s->cx, s->cy, {0.f, 0.f, 0.f, 0.f, 0.f}};
+    if (r) {
+        h->rgbd = true;
+        h->rs = *r;
+        for (int k = 0; k < r->ndist; k++) h->ucam.dist[k] = r->dist[k];
+    }
+    // a stereo handle's frames are rectified (no distortion): 0, width, 0, height
+    orbmi::image_bounds(h->ucam, s->height, s->width, h->bounds);
     int rc = orbmi_extractor_create(device, s->n_features, s->scale_factor, s->n_levels, s->ini_th_fast, s->min_th_fast,
                                     &h->left);
-    if (!rc) rc = orbmi_extractor_create(device, s->n_features, s->scale_factor, s->n_levels, s->ini_th_fast,
-                                         s->min_th_fast, &h->right);
+    if (!rc && !r) rc = orbmi_extractor_create(device, s->n_features, s->scale_factor, s->n_levels, s->ini_th_fast,
+                                               s->min_th_fast, &h->right);
     if (!rc) {
         void* xs = nullptr;
         rc = orbmi_extractor_get_stream(h->left, &xs);
@@ -2842,6 +2919,18 @@ int orbmi_slam_create(const orbmi_slam_settings* s, int device, orbmi_vocabulary
     if (h->async_lm()) h->lm_thread = std::thread([h] { h->lm_run(); });
     *out = h;
     return ORBMI_OK;
+}
+
+extern "C" {
+
+int orbmi_slam_create(const orbmi_slam_settings* s, int device, orbmi_vocabulary* vocabulary, orbmi_slam** out) {
+    return slam_create(s, nullptr, device, vocabulary, out);
+}
+
+int orbmi_slam_create_rgbd(const orbmi_slam_settings* s, const orbmi_rgbd_settings* r, int device,
+                           orbmi_vocabulary* vocabulary, orbmi_slam** out) {
+    if (!r) return ORBMI_E_ARG;
+    return slam_create(s, r, device, vocabulary, out);
 }
 
 int orbmi_slam_wait_local_mapping(orbmi_slam* h) {
@@ -2908,6 +2997,7 @@ static int track_stereo(orbmi_slam* h, const uint8_t* left, const uint8_t* right
                         double timestamp, const uint8_t* next_left, const uint8_t* next_right, bool ahead, float* tcw_out,
                         int* has_pose) {
     if (!h || !left || !right || rows <= 0 || cols <= 0 || step < (size_t)cols) return ORBMI_E_ARG;
+    if (h->rgbd) return ORBMI_E_STATE;
     if (h->reset_pending) SLAM_CHECK(h->deferred_reset());  // (src/System.cc:139-146)
     TrackedFrame cf;
     cf.id = h->frame_count;
@@ -2943,6 +3033,27 @@ int orbmi_slam_track_stereo_ahead(orbmi_slam* h, const uint8_t* left, const uint
                                   size_t step, double timestamp, const uint8_t* next_left, const uint8_t* next_right,
                                   float* tcw_out, int* has_pose) {
     return track_stereo(h, left, right, rows, cols, step, timestamp, next_left, next_right, true, tcw_out, has_pose);
+}
+
+int orbmi_slam_track_rgbd(orbmi_slam* h, const uint8_t* image, int channels, size_t image_step, const void* depth,
+                          int depth_type, size_t depth_step, int rows, int cols, double timestamp, float* tcw_out,
+                          int* has_pose) {
+    if (!h || !image || !depth || rows <= 0 || cols <= 0 || (channels != 1 && channels != 3 && channels != 4) ||
+        image_step < (size_t)cols * channels || (depth_type != ORBMI_DEPTH_F32 && depth_type != ORBMI_DEPTH_U16) ||
+        depth_step < (size_t)cols * (depth_type == ORBMI_DEPTH_U16 ? 2 : 4) || rows > 65535)
+        return ORBMI_E_ARG;
+    if (!h->rgbd) return ORBMI_E_STATE;
+    if (h->reset_pending) SLAM_CHECK(h->deferred_reset());  // (src/System.cc:190-197)
+    TrackedFrame cf;
+    cf.id = h->frame_count;
+    cf.ts = timestamp;
+    PhaseTimer total(&h->phase_ms[PH_TOTAL]);
+    h->phase_frames++;
+    {
+        PhaseTimer pt(&h->phase_ms[PH_FRAME]);
+        SLAM_CHECK(h->frame_rgbd(cf, image, channels, image_step, depth, depth_type, depth_step, rows, cols));
+    }
+    return track_frame(h, cf, tcw_out, has_pose);
 }
 
 int orbmi_slam_get_schedule(orbmi_slam* h, orbmi_slam_event* out, int capacity, int* n) {

@@ -22,6 +22,11 @@ class SlamSettings(C.Structure):
                 ("async_local_mapping", C.c_int)]
 
 
+class RgbdSettings(C.Structure):
+    """orbmi_rgbd_settings (include/orbmi.h)."""
+    _fields_ = [("dist", C.c_float * 5), ("ndist", C.c_int), ("depth_map_factor", C.c_float), ("rgb", C.c_int)]
+
+
 class FrameStats(C.Structure):
     _fields_ = [(k, C.c_int) for k in ("frame", "n", "state", "init", "track", "lf_matches", "bow_matches",
                                        "nmatches_map", "local_map_points", "local_matches", "inliers", "need_kf",
@@ -36,8 +41,9 @@ class NativeStereoSLAM:
     one dict per frame with the counters the stage that ran produced."""
 
     def __init__(self, settings, device: int = 0, vocabulary=None, local_ba: bool = True, local_mapping: bool = True,
-                 async_local_mapping: bool = False, record: bool = False):
-        """record: keep the schedule, the LocalBA log and the per-keyframe state log
+                 async_local_mapping: bool = False, record: bool = False, sensor: str = "stereo"):
+        """sensor: "stereo" (TrackStereo) or "rgbd" (TrackRGBD, orbmi_slam_create_rgbd: the settings'
+        distortion coefficients, DepthMapFactor and Camera.RGB).  record: keep the schedule, the LocalBA log and the per-keyframe state log
         (orbmi_slam_set_recording) for schedule(), local_ba_log() and keyframe_state_log()."""
         from .settings import Settings, load_settings
         s = settings if isinstance(settings, Settings) else load_settings(settings)
@@ -53,8 +59,20 @@ class NativeStereoSLAM:
                          float(s.scale_factor), int(s.n_levels), int(s.ini_th_fast), int(s.min_th_fast),
                          1 if local_ba else 0, 1 if local_mapping else 0, 1 if async_local_mapping else 0)
         h = C.c_void_p()
-        check("orbmi_slam_create", lib().orbmi_slam_create(C.addressof(c), device,
-                                                           self._voc._h if self._voc else None, C.byref(h)))
+        if sensor not in ("stereo", "rgbd"):
+            raise ValueError("sensor is 'stereo' or 'rgbd'")
+        self.sensor = sensor
+        if sensor == "rgbd":
+            r = RgbdSettings()
+            d = np.asarray(s.dist_coef, np.float32).ravel()
+            for k, v in enumerate(d):
+                r.dist[k] = float(v)
+            r.ndist, r.depth_map_factor, r.rgb = len(d), float(s.depth_map_factor), int(bool(s.rgb))
+            check("orbmi_slam_create_rgbd", lib().orbmi_slam_create_rgbd(
+                C.addressof(c), C.addressof(r), device, self._voc._h if self._voc else None, C.byref(h)))
+        else:
+            check("orbmi_slam_create", lib().orbmi_slam_create(C.addressof(c), device,
+                                                               self._voc._h if self._voc else None, C.byref(h)))
         self._h = h
         self._tcw = np.zeros(16, np.float32)
         if record:
@@ -85,6 +103,24 @@ class NativeStereoSLAM:
                 None if nL is None else nL.ctypes.data, None if nR is None else nR.ctypes.data,
                 self._tcw.ctypes.data, C.byref(has)))
             self._ahead = (nL, nR) if nL is not None else None  # the buffers stay alive until used
+        return self._tcw.reshape(4, 4).copy() if has.value else None
+
+    def TrackRGBD(self, im, depthmap, timestamp: float):
+        """System::TrackRGBD: im u8 gray or H x W x 3|4 (Camera.RGB order), depthmap float32 or
+        uint16 of the same size (orbmi_slam_track_rgbd)."""
+        from .orb import _depth_args
+        im = np.asarray(im)
+        if im.dtype != np.uint8 or im.ndim not in (2, 3):
+            raise ValueError("TrackRGBD expects a u8 gray or colour image")
+        im = np.ascontiguousarray(im)
+        ch = 1 if im.ndim == 2 else im.shape[2]
+        depth, dtype, dstep = _depth_args(depthmap)
+        if depth.shape != im.shape[:2]:
+            raise ValueError("the depth map has the image's size")
+        has = C.c_int()
+        check("orbmi_slam_track_rgbd", lib().orbmi_slam_track_rgbd(
+            self._h, im.ctypes.data, ch, im.strides[0], depth.ctypes.data, dtype, dstep, im.shape[0], im.shape[1],
+            float(timestamp), self._tcw.ctypes.data, C.byref(has)))
         return self._tcw.reshape(4, 4).copy() if has.value else None
 
     def counts(self):

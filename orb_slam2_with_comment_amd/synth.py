@@ -6,7 +6,8 @@ x=+-8 m, a canopy at y=-4 m and a far wall, camera moving forward 1 m/frame with
 yaw.  Intrinsics come from the reference's own settings files
 (Examples/Stereo/KITTI00-02.yaml, Examples/Monocular/EuRoC.yaml).  The texture is a blocky
 multi-scale hash pattern on a smooth gradient plus +-4 uniform noise, seeded per frame, which
-gives FAST corners at every pyramid level.
+gives FAST corners at every pyramid level.  `rgbd_frame` renders the same scene at indoor size
+through the distortion model of Examples/RGB-D/TUM1.yaml, with a uint16 depth map.
 """
 from __future__ import annotations
 
@@ -34,6 +35,22 @@ class Camera:
 KITTI = Camera(1241, 376, 718.856, 718.856, 607.1928, 185.2157, 386.1448)
 # Examples/Monocular/EuRoC.yaml (bf from Examples/Stereo/EuRoC.yaml)
 EUROC = Camera(752, 480, 458.654, 457.296, 367.215, 248.375, 47.90639384423901)
+
+
+
+@dataclasses.dataclass(frozen=True)
+class RGBDCamera(Camera):
+    """A distorted RGB-D camera: mDistCoef (k1 k2 p1 p2 k3), ThDepth and DepthMapFactor as the
+    settings file gives them."""
+    dist_coef: tuple = (0.0, 0.0, 0.0, 0.0)
+    th_depth: float = 40.0
+    depth_map_factor: float = 5000.0
+    n_features: int = 1000
+
+
+# Examples/RGB-D/TUM1.yaml (bf 40, ThDepth 40, DepthMapFactor 5000, 1000 features)
+TUM1 = RGBDCamera(640, 480, 517.306408, 516.469215, 318.643040, 255.313989, 40.0,
+                  (0.262383, -0.953104, -0.005358, 0.002628, 1.163314), 40.0, 5000.0, 1000)
 
 _PLANES = (  # (axis, offset): plane axis == offset in world coordinates
     (1, 1.65),    # ground
@@ -106,3 +123,76 @@ def stereo_pair(cam: Camera, frame: int, seed_base: int = 1000):
 
 def mono(cam: Camera, frame: int, seed_base: int = 5000):
     return render(cam, pose(frame, step=0.05, yaw_deg=0.5), seed_base + frame)
+
+
+# ---- RGB-D (TUM-shaped) ---------------------------------------------------------------------
+_ROOM = (  # (axis, offset) in metres: an indoor corridor around a camera 1 m above the floor
+    (1, 1.0),     # floor
+    (1, -1.2),    # ceiling
+    (0, -1.5),    # left wall
+    (0, 1.5),     # right wall
+    (2, 10.0),    # end wall (beyond the sensor range until the camera gets close)
+)
+_ROOM_TEXTURE_SCALE = 0.25   # the KITTI-shaped texture shrunk 4x: 15 cm and 4 cm blocks
+_RGBD_STEP = 0.05            # metres per frame
+_RGBD_RANGE = 6.0            # metres; farther surfaces read 0 (a dropout)
+
+
+def _undistorted_rays(cam) -> np.ndarray:
+    """Per pixel of the distorted image, the undistorted normalised point (x, y, 1): the
+    distortion model inverted by the five fixed-point iterations cv::undistortPoints runs."""
+    k1, k2, p1, p2 = cam.dist_coef[:4]
+    k3 = cam.dist_coef[4] if len(cam.dist_coef) > 4 else 0.0
+    u = np.arange(cam.width, dtype=np.float64)
+    v = np.arange(cam.height, dtype=np.float64)
+    uu, vv = np.meshgrid(u, v)
+    x0, y0 = (uu - cam.cx) / cam.fx, (vv - cam.cy) / cam.fy
+    x, y = x0, y0
+    for _ in range(5):
+        r2 = x * x + y * y
+        icdist = 1.0 / (1.0 + ((k3 * r2 + k2) * r2 + k1) * r2)
+        dx = 2 * p1 * x * y + p2 * (r2 + 2 * x * x)
+        dy = p1 * (r2 + 2 * y * y) + 2 * p2 * x * y
+        x, y = (x0 - dx) * icdist, (y0 - dy) * icdist
+    return np.stack([x, y, np.ones_like(x)], -1)
+
+
+def rgbd_frame(cam: RGBDCamera, frame: int, seed_base: int = 9000, noise: float = 4.0):
+    """(rgb u8 H x W x 3, depth u16 H x W, Twc) of frame `frame` of the TUM-shaped sequence.
+
+    The scene is the KITTI-shaped one at indoor size: a corridor 3 m wide and 2.2 m high (_ROOM)
+    with the texture at scale 0.25, the camera moving 0.05 m/frame forward with 0.2 deg/frame yaw.
+    Rendering goes through the distortion model: the ray of a pixel is its undistorted normalised
+    point, so undistorted keypoints obey the pinhole model of K.  depth = z * DepthMapFactor as
+    uint16, 0 beyond 6 m (sensor dropouts: the end wall at the start).  The chosen scale: walls
+    1.5 m to either side, floor 1.0 m below, ceiling 1.2 m above, end wall 10 m ahead, texture
+    blocks of 15 cm and 4 cm.  With TUM1 frame 0 gives 1,004 keypoints, 711 of them with depth
+    (more than the 500 StereoInitialization asks for, src/Tracking.cc:586) and 104 closer than
+    mThDepth = bf ThDepth / fx = 3.09 m (tests/test_rgbd_cpu.py checks both conditions)."""
+    Twc = pose(frame, step=_RGBD_STEP)
+    dc = _undistorted_rays(cam)
+    dw = dc @ Twc[:3, :3].T
+    o = Twc[:3, 3]
+    best_t = np.full(dc.shape[:2], np.inf)
+    img = np.zeros(dc.shape[:2])
+    for pid, (axis, off) in enumerate(_ROOM):
+        with np.errstate(divide="ignore", invalid="ignore"):
+            t = (off - o[axis]) / dw[..., axis]
+        hit = (t > 0) & (t < best_t)
+        if not hit.any():
+            continue
+        p = (o + dw[hit] * t[hit][:, None]) / _ROOM_TEXTURE_SCALE
+        ax = [k for k in range(3) if k != axis]
+        a, b = p[:, ax[0]], p[:, ax[1]]
+        val = 128.0 + 50.0 * np.sin(0.11 * a + pid) * np.cos(0.07 * b)
+        val += 80.0 * (_hash01(np.floor(a / 0.6), np.floor(b / 0.6), 11 + pid) - 0.5)
+        val += 50.0 * (_hash01(np.floor(a / 0.17), np.floor(b / 0.17), 23 + pid) - 0.5)
+        img[hit] = val
+        best_t[hit] = t[hit]
+    rng = np.random.default_rng(seed_base + frame)
+    img += rng.uniform(-noise, noise, img.shape)
+    g = np.rint(img)
+    rgb = np.clip(np.stack([g + 6, g, g - 9], -1), 0, 255).astype(np.uint8)  # a slight tint: R, G, B differ
+    z = np.where(np.isfinite(best_t) & (best_t <= _RGBD_RANGE), best_t, 0.0)  # t along (x, y, 1) is the depth
+    depth = np.clip(np.rint(z * cam.depth_map_factor), 0, 65535).astype(np.uint16)
+    return rgb, depth, Twc

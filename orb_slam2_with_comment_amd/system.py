@@ -407,6 +407,8 @@ class GpuBackend:
         from .optimizer import LocalBA, PoseOptimizer
         from .orb import ORBextractor
         s = settings
+        self.settings = s
+        self.device = device
         self.left = ORBextractor(s.n_features, float(s.scale_factor), s.n_levels, s.ini_th_fast, s.min_th_fast,
                                  device=device)
         self.right = ORBextractor(s.n_features, float(s.scale_factor), s.n_levels, s.ini_th_fast, s.min_th_fast,
@@ -436,6 +438,21 @@ class GpuBackend:
             dl = np.zeros((0, 32), np.uint8)
         u, d = compute_stereo_matches(self.left, self.right, self.cam_bf, self.cam_fx, n)
         return kl, dl, u, d
+
+    def extract_rgbd(self, im, depth):
+        """Tracking::GrabImageRGBD + Frame::Frame (RGB-D) (src/Tracking.cc:208-230, src/Frame.cc:
+        119-171): cvtColor for a colour image, ORBextractor, UndistortKeyPoints and
+        ComputeStereoFromRGBD -> mvKeysUn, desc, mvuRight, mvDepth."""
+        from .orb import compute_stereo_from_rgbd, cvt_gray
+        s = self.settings
+        im = np.asarray(im)
+        gray = cvt_gray(im, s.rgb, self.device) if im.ndim == 3 else im
+        k, dsc = self.left(gray)
+        if dsc is None:
+            dsc = np.zeros((0, 32), np.uint8)
+        ku, u, d = compute_stereo_from_rgbd(self.left, depth, float(s.depth_map_factor), s, s.dist_coef, self.cam_bf,
+                                            len(k))
+        return ku, dsc, u, d
 
     def bind_camera(self, cam):
         self.cam_bf, self.cam_fx = float(cam.bf), float(cam.fx)
@@ -519,16 +536,30 @@ class StereoSLAM:
     initialised / lost), as System::TrackStereo returns mCurrentFrame.mTcw."""
 
     def __init__(self, settings, backend=None, device: int = 0, vocabulary=None, local_ba: bool = True,
-                 local_mapping: bool = True):
+                 local_mapping: bool = True, sensor: str = "stereo"):
+        """sensor: "stereo" (System::STEREO, TrackStereo) or "rgbd" (System::RGBD, TrackRGBD).  The
+        reference takes the same branches for both after the Frame constructor."""
         from .settings import Settings, load_settings
         self.settings = settings if isinstance(settings, Settings) else load_settings(settings)
         s = self.settings
         if s.width <= 0 or s.height <= 0:
             raise ValueError("settings need Camera.width / Camera.height")
+        if sensor not in ("stereo", "rgbd"):
+            raise ValueError("sensor is 'stereo' or 'rgbd'")
+        self.sensor = sensor
         self.cam = s.camera
         self.backend = backend if backend is not None else GpuBackend(s, device, vocabulary)
         if hasattr(self.backend, "bind_camera"):
             self.backend.bind_camera(self.cam)
+        # mnMinX, mnMaxX, mnMinY, mnMaxY (Frame::ComputeImageBounds), once per system; None = the
+        # undistorted 0, width, 0, height of the rectified stereo rig
+        self.bounds = None
+        if sensor == "rgbd":
+            if hasattr(self.backend, "image_bounds"):
+                self.bounds = tuple(self.backend.image_bounds(s))
+            else:
+                from .orb import compute_image_bounds
+                self.bounds = tuple(compute_image_bounds(s, s.dist_coef, s.height, s.width))
         self.use_local_ba = local_ba
         # LocalMapping::Run in full (MapPointCulling, CreateNewMapPoints, SearchInNeighbors,
         # KeyFrameCulling); False keeps ProcessNewKeyFrame + MapPointCulling + LocalBA only
@@ -567,7 +598,22 @@ class StereoSLAM:
         self._ba_stop_at = None   # kf -> the pbStopFlag check a LocalBA stops at (-1: none)
 
     # ---- System::TrackStereo ----------------------------------------------------------------
+    def TrackRGBD(self, im, depthmap, timestamp: float):
+        """System::TrackRGBD (src/System.cc:161-210): im u8 gray or H x W x 3|4 (Camera.RGB order),
+        depthmap float32 or uint16 (scaled by the settings' DepthMapFactor)."""
+        if self.sensor != "rgbd":
+            raise RuntimeError("TrackRGBD on a system that is not RGBD (src/System.cc:163-167)")
+        keys, desc, u_right, depth = self.backend.extract_rgbd(im, depthmap)
+        n = len(keys)
+        cf = TrackedFrame(self.frame_count, float(timestamp), keys, desc.reshape(-1, 32), u_right, depth,
+                          map_points=[None] * n, outlier=np.zeros(n, bool))
+        self.frame_count += 1
+        self._track(cf)
+        return None if cf.tcw is None else cf.tcw.copy()
+
     def TrackStereo(self, imLeft, imRight, timestamp: float):
+        if self.sensor != "stereo":
+            raise RuntimeError("TrackStereo on a system that is not STEREO (src/System.cc:112-116)")
         keys, desc, u_right, depth = self.backend.extract_stereo(imLeft, imRight)
         n = len(keys)
         cf = TrackedFrame(self.frame_count, float(timestamp), keys, desc.reshape(-1, 32), u_right, depth,
@@ -588,7 +634,7 @@ class StereoSLAM:
 
     def _frame(self, f: TrackedFrame, tcw=None) -> Frame:
         return Frame(f.keys, f.desc, f.u_right, f.tcw if tcw is None else tcw, self.cam, self.backend.scale_factors,
-                     self.cam.width, self.cam.height)
+                     self.cam.width, self.cam.height, self.bounds)
 
     def _track(self, cf: TrackedFrame):
         return self._drain(self._track_gen(cf))
@@ -936,7 +982,7 @@ class StereoSLAM:
 
     def _kf_frame(self, kf: KeyFrame) -> Frame:
         return Frame(kf.keys_un, kf.desc, kf.u_right, kf.tcw, self.cam, self.backend.scale_factors,
-                     self.cam.width, self.cam.height)
+                     self.cam.width, self.cam.height, self.bounds)
 
     def _create_new_map_points_gen(self, kf: KeyFrame):
         """LocalMapping::CreateNewMapPoints (src/LocalMapping.cc:290-577), stereo: the 10 best
@@ -1410,7 +1456,7 @@ class StereoSLAM:
         ok_mp = np.array([mp is not None and not mp.bad for mp in kf.map_points], np.uint8)
         kf_mps = list(kf.map_points)   # the keyframe's matches when the search ran
         kfv = Frame(kf.keys_un, kf.desc, kf.u_right, kf.tcw, self.cam, self.backend.scale_factors,
-                    self.cam.width, self.cam.height)
+                    self.cam.width, self.cam.height, self.bounds)
         m, n = self.backend.search_by_bow(kfv, ok_mp, kf.feat_vec, self._frame(cf, np.eye(4)), cf.feat_vec)
         yield T_BOW, cf.id
         st["bow_matches"] = n

@@ -48,7 +48,9 @@ class Frame:
     """Host-side Frame data the matchers read (include/Frame.h), kept alive for the views."""
 
     def __init__(self, keys, desc, u_right=None, tcw=None, cam=None, scale_factors=None, width=None,
-                 height=None):
+                 height=None, bounds=None):
+        """bounds = (mnMinX, mnMaxX, mnMinY, mnMaxY) of a distorted camera
+        (orb.compute_image_bounds); default: 0, width, 0, height (no distortion)."""
         self.keys = np.ascontiguousarray(keys, KP_DTYPE)
         self.desc = np.ascontiguousarray(desc, np.uint8).reshape(-1, 32)
         self.u_right = None if u_right is None else np.ascontiguousarray(u_right, np.float32)
@@ -63,6 +65,7 @@ class Frame:
         self.scale_factors = np.ascontiguousarray(scale_factors, np.float32)
         self.width = width if width is not None else cam.width
         self.height = height if height is not None else cam.height
+        self.bounds = None if bounds is None else tuple(np.float32(b) for b in bounds)
 
     def view(self) -> FrameView:
         v = FrameView()
@@ -74,10 +77,16 @@ class Frame:
         c = self.cam
         v.fx, v.fy, v.cx, v.cy, v.bf = c.fx, c.fy, c.cx, c.cy, c.bf
         v.mb = np.float32(np.float32(c.bf) / np.float32(c.fx))
-        # ComputeImageBounds without distortion (src/Frame.cc:481-498)
-        v.min_x, v.max_x, v.min_y, v.max_y = 0.0, float(self.width), 0.0, float(self.height)
-        v.grid_w_inv = np.float32(np.float32(FRAME_GRID_COLS) / np.float32(self.width))
-        v.grid_h_inv = np.float32(np.float32(FRAME_GRID_ROWS) / np.float32(self.height))
+        if self.bounds is None:
+            # ComputeImageBounds without distortion (src/Frame.cc:481-498)
+            v.min_x, v.max_x, v.min_y, v.max_y = 0.0, float(self.width), 0.0, float(self.height)
+            v.grid_w_inv = np.float32(np.float32(FRAME_GRID_COLS) / np.float32(self.width))
+            v.grid_h_inv = np.float32(np.float32(FRAME_GRID_ROWS) / np.float32(self.height))
+        else:  # (src/Frame.cc:153-156)
+            x0, x1, y0, y1 = self.bounds
+            v.min_x, v.max_x, v.min_y, v.max_y = x0, x1, y0, y1
+            v.grid_w_inv = np.float32(np.float32(FRAME_GRID_COLS) / np.float32(x1 - x0))
+            v.grid_h_inv = np.float32(np.float32(FRAME_GRID_ROWS) / np.float32(y1 - y0))
         v.nlevels = len(self.scale_factors)
         v.scale_factors = self.scale_factors.ctypes.data
         v.log_scale_factor = np.float32(np.log(np.float32(self.scale_factors[1]))) if len(self.scale_factors) > 1 else 0.0
