@@ -685,6 +685,89 @@ int orbmi_create_new_map_points(orbmi_matcher* m, const orbmi_frame_view* kf1, c
                                 const orbmi_feature_vector* fv2, const float* F12, int32_t* match12, uint8_t* ok,
                                 float* x3d);
 
+/* One LocalMapping::Run iteration for a new keyframe (src/LocalMapping.cc:47-128) as one call:
+ * what the per-operator entries above do when called one after the other, staged once.  Every
+ * array is device memory unless noted; every output is device memory (the call reads none of
+ * them back), except the LocalBA result. */
+typedef struct orbmi_lm_job {
+    /* KeyFrame::ComputeBoW (ProcessNewKeyFrame, :152-160).  voc != NULL: orbmi_transform of
+     * bow_desc (bow_n x 32) is issued here, and its sizes copied to counts_host behind it.
+     * voc == NULL: the caller issued both ahead (on any stream).  Either way counts_event is
+     * recorded (by the caller when voc == NULL, here otherwise) behind the copy of the two size
+     * words to counts_host (pinned host memory): the call waits on that event only. */
+    orbmi_vocabulary* voc;
+    const uint8_t* bow_desc;
+    int bow_n;
+    uint32_t* bow_word;            /* the keyframe's BowVector / FeatureVector set, as          */
+    double* bow_value;             /* orbmi_transform writes it (capacity bow_n)               */
+    uint32_t* fv_node;
+    int32_t* fv_off;
+    int32_t* fv_feat;
+    int* bow_counts;               /* device: words, nodes                                     */
+    const int32_t* counts_host;    /* pinned host: words, nodes                                */
+    void* counts_event;            /* hipEvent_t behind the copy to counts_host                */
+    /* MapPoint::ComputeDistinctiveDescriptors of the keyframe's points (:162-190 and :662-674),
+     * as orbmi_compute_distinctive_descriptors; run before CreateNewMapPoints and after Fuse. */
+    const uint8_t* obs_desc;
+    const int32_t* obs_off;
+    int n_points;
+    int32_t* best;
+    uint8_t* desc_out;
+    /* CreateNewMapPoints (:290-577), as orbmi_create_new_map_points; fv1 = the set above with
+     * the node count read from counts_host. */
+    const orbmi_frame_view* kf;
+    const orbmi_tri_keyframe* tri;
+    const float* cos;
+    const uint8_t* has_mp;
+    int nnb;                       /* neighbours (may be 0: no search, no batched Fuse)         */
+    const orbmi_frame_view* kf2;
+    const orbmi_tri_keyframe* tri2;
+    const float* const* cos2;
+    const uint8_t* const* has_mp2;
+    const orbmi_feature_vector* fv2;
+    const float* F12;              /* host, 9 x nnb                                             */
+    int32_t* match12;              /* nnb x kf->n                                               */
+    uint8_t* ok;
+    float* x3d;
+    /* SearchInNeighbors (:589-660): orbmi_fuse_search_batch(kf2[0..nnb), kf_points) into
+     * best_idx / best_dist[0 .. nnb * n_kf_points), then orbmi_fuse_search(kf, target_points)
+     * into the n_target_points entries behind them. */
+    const orbmi_mappoint* kf_points;
+    int n_kf_points;
+    const orbmi_mappoint* target_points;
+    int n_target_points;
+    float fuse_th;                 /* 3.0 in the reference                                      */
+    int32_t* best_idx;
+    int32_t* best_dist;
+    /* Optimizer::LocalBundleAdjustment (:89-90), as orbmi_local_bundle_adjustment. */
+    const orbmi_ba_problem* problem;
+    orbmi_ba_result* result;
+    const volatile int* stop;
+    /* optional diagnostics: 4 hipEvent_t recorded on the matcher's stream behind ComputeBoW +
+     * the first ComputeDistinctiveDescriptors, CreateNewMapPoints, the Fuse searches and the
+     * second ComputeDistinctiveDescriptors (NULL: none) */
+    void* const* stage_events;
+} orbmi_lm_job;
+
+typedef struct orbmi_lm_job_result {
+    int bow_words, fv_nodes;       /* sizes of the keyframe's BowVector / FeatureVector         */
+    int failed_stage;              /* -1, or the stage that returned the error: 0 ComputeBoW,
+                                    * 1 / 4 ComputeDistinctiveDescriptors, 2 CreateNewMapPoints,
+                                    * 3 Fuse, 5 LocalBundleAdjustment                           */
+} orbmi_lm_job_result;
+
+/* LocalMapping::Run's body for one keyframe (src/LocalMapping.cc:47-128, the calls it replaces:
+ * ProcessNewKeyFrame :59, CreateNewMapPoints :65, SearchInNeighbors :70, LocalBundleAdjustment
+ * :89-90) on the matcher's stream, in the reference's order, LocalBA through `ba` (run it on the
+ * matcher's stream, orbmi_ba_set_stream, for an in-order chain).  The host tables of all the
+ * searches (pair table, KF2 sides, Fuse keyframes) are validated and built inside the call and go
+ * to the device in one copy into one arena generation.  The only host waits are counts_event
+ * (the FeatureVector's node count sizes the triangulation search) and LocalBA's own.  Returns
+ * when LocalBA has returned; the first failing stage's code otherwise (failed_stage), with
+ * nothing left pending in the matcher's arena.  ba's enqueued hook fires as in
+ * orbmi_local_bundle_adjustment. */
+int orbmi_local_mapping_job(orbmi_matcher* m, orbmi_ba* ba, const orbmi_lm_job* job, orbmi_lm_job_result* result);
+
 /* ---- System::TrackStereo: the native stereo SLAM host loop ---------------------------- */
 
 /* The Tracking constructor's view of a settings file (src/Tracking.cc:53-143) for a rectified

@@ -119,6 +119,7 @@ _PROTOS = {
     "orbmi_fuse_search_refresh": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, C.c_float, _vp, _vp]),
     "orbmi_create_new_map_points": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                          _vp]),
+    "orbmi_local_mapping_job": (_i, [_vp, _vp, _vp, _vp]),
     "orbmi_compute_image_bounds": (_i, [_f, _f, _f, _f, _vp, _i, _i, _i, _vp]),
     "orbmi_compute_stereo_from_rgbd": (_i, [_vp, _i, _vp, _i, _sz, _f, _i, _i, _vp, _f, _vp, _vp, _vp, _i]),
     "orbmi_compute_stereo_from_rgbd_keys": (_i, [_i, _vp, _i, _vp, _i, _sz, _f, _i, _i, _vp, _f, _vp, _vp, _vp]),

@@ -257,6 +257,147 @@ int scalars(Matcher& m) {
     return ORBMI_OK;
 }
 
+// CreateNewMapPoints in two halves, shared by orbmi_create_new_map_points and
+// orbmi_local_mapping_job: cnmp_stage validates the pairs and stages everything that does not
+// depend on KF1's FeatureVector (frames, triangulation sides, the pair table and the KF2 sides
+// in one upload), cnmp_launch enqueues the searches and the geometry.
+struct CnmpPlan {
+    DevFrame K1;
+    const uint8_t* has1 = nullptr;
+    orbmi::tri::Side S1;
+    int npairs = 0;
+    std::vector<DevFrame> KF2;  // the neighbours' frames (the batched Fuse of a job reuses them)
+    TriPair* d_pairs = nullptr;
+    const orbmi::tri::Side* d_S2 = nullptr;
+    int* d_match = nullptr;
+    uint8_t* d_ok = nullptr;
+    float* d_x3d = nullptr;
+};
+
+int cnmp_stage(Matcher& m, const orbmi_frame_view* kf1, const orbmi_tri_keyframe* tri1, const float* cos1,
+               const uint8_t* has_mp1, int npairs, const orbmi_frame_view* kf2, const orbmi_tri_keyframe* tri2,
+               const float* const* cos2, const uint8_t* const* has_mp2, const orbmi_feature_vector* fv2,
+               const float* F12, int32_t* match12, uint8_t* ok, float* x3d, std::vector<OutBuf>& outs, CnmpPlan* P) {
+    if (!kf1 || !tri1 || !has_mp1 || !kf1->u_right || npairs <= 0 || !kf2 || !tri2 || !has_mp2 || !fv2 || !F12 ||
+        !match12 || !ok || !x3d)
+        return ORBMI_E_ARG;
+    int rc;
+    DevFrame& K1 = P->K1;
+    if ((rc = make_frame(m, kf1, &K1, true))) return rc;
+    const size_t n1 = (size_t)std::max(K1.n, 1);
+    P->has1 = dev_in(m, has_mp1, n1, &rc);
+    if (rc) return rc;
+    std::vector<std::vector<float>> cos_tmp;  // tables computed here (copied into the arena's mirror at once)
+    cos_tmp.reserve((size_t)npairs + 1);
+    // the triangulation side of a keyframe: keys / u_right from its frame view (device), the rest
+    // from its tri view
+    auto side = [&](const orbmi_tri_keyframe* T, const orbmi_frame_view* v, const DevFrame& D, const float* cs,
+                    orbmi::tri::Side* S) -> int {
+        if (!T->tcw || !T->depth || !T->level_sigma2 || !T->scale_factors || on_device(T->level_sigma2) ||
+            on_device(T->scale_factors) || v->nlevels > orbmi::tri::kLevels)
+            return ORBMI_E_ARG;
+        orbmi::tri::make_side(*T, v->nlevels, S);
+        S->keys = D.keys;
+        S->ur = D.u_right;
+        int r = 0;
+        S->depth = dev_in(m, T->depth, (size_t)D.n, &r);
+        if (r) return r;
+        if (!cs) {
+            if (on_device(T->depth)) return ORBMI_E_ARG;
+            cos_tmp.emplace_back((size_t)std::max(D.n, 1));
+            if ((r = orbmi_stereo_parallax_cos(T->mb, T->depth, D.n, cos_tmp.back().data()))) return r;
+            cs = cos_tmp.back().data();
+        }
+        S->cos_stereo = dev_in(m, cs, (size_t)D.n, &r);
+        return r;
+    };
+    if ((rc = side(tri1, kf1, K1, cos1, &P->S1))) return rc;
+    std::vector<orbmi::tri::Side> S2(npairs);
+    std::vector<TriPair> pairs(npairs);
+    const bool F_dev = on_device(F12);
+    std::vector<float> Fh((size_t)9 * npairs);
+    if (F_dev) ORBMI_HIP(hipMemcpy(Fh.data(), F12, Fh.size() * sizeof(float), hipMemcpyDeviceToHost));
+    else memcpy(Fh.data(), F12, Fh.size() * sizeof(float));
+    P->KF2.resize(npairs);
+    for (int j = 0; j < npairs; j++) {
+        TriPair& T = pairs[j];
+        memset(&T, 0, sizeof(T));
+        if (!kf2[j].u_right || !has_mp2[j]) return ORBMI_E_ARG;
+        if ((rc = make_frame(m, &kf2[j], &T.KF2, true))) return rc;
+        P->KF2[j] = T.KF2;
+        if ((rc = make_fv(m, &fv2[j], &T.fv2))) return rc;
+        T.has_mp2 = dev_in(m, has_mp2[j], (size_t)std::max(T.KF2.n, 1), &rc);
+        if (rc) return rc;
+        for (int q = 0; q < 9; q++) T.F12.m[q] = Fh[9 * j + q];
+        if ((rc = side(&tri2[j], &kf2[j], T.KF2, cos2 ? cos2[j] : nullptr, &S2[j]))) return rc;
+    }
+    P->npairs = npairs;
+    P->d_match = dev_out(m, match12, (size_t)K1.n * npairs, outs);
+    P->d_ok = dev_out(m, ok, (size_t)K1.n * npairs, outs);
+    P->d_x3d = dev_out(m, x3d, (size_t)3 * K1.n * npairs, outs);
+    if (!P->d_match || !P->d_ok || !P->d_x3d) return ORBMI_E_HIP;
+    if ((rc = orbmi::tri_pairs_prepare(m, K1, npairs, pairs.data(), P->d_match))) return rc;
+    // the pair table and the KF2 sides go up in one copy
+    const size_t o_s2 = (sizeof(TriPair) * npairs + 255) & ~(size_t)255;
+    const size_t tab_bytes = o_s2 + sizeof(orbmi::tri::Side) * npairs;
+    std::vector<uint8_t> tab(tab_bytes);
+    memcpy(tab.data(), pairs.data(), sizeof(TriPair) * npairs);
+    memcpy(tab.data() + o_s2, S2.data(), sizeof(orbmi::tri::Side) * npairs);
+    uint8_t* d_tab = (uint8_t*)m.stage(tab_bytes);
+    if (!d_tab) return ORBMI_E_HIP;
+    ORBMI_HIP(m.h2d(d_tab, tab.data(), tab_bytes));
+    P->d_pairs = (TriPair*)d_tab;
+    P->d_S2 = (const orbmi::tri::Side*)(d_tab + o_s2);
+    return ORBMI_OK;
+}
+
+int cnmp_launch(Matcher& m, const CnmpPlan& P, const DevFV& f1) {
+    return orbmi::launch_create_points(m, P.K1, P.has1, f1, P.npairs, nullptr, P.d_pairs, P.S1, P.d_S2, P.d_match, P.d_ok,
+                                       P.d_x3d);
+}
+
+// The batched Fuse search in the same two halves: fuse_batch_stage builds and uploads the
+// keyframe table (frames: the keyframes' views already resolved, or nullptr), fuse_batch_launch
+// enqueues the grids and the search.
+struct FusePlan {
+    int nkf = 0, n = 0, ncap = 0;
+    FuseKF* d_k = nullptr;
+    int* d_cnt = nullptr;
+    const orbmi_mappoint* d_mps = nullptr;
+    int* d_bi = nullptr;
+    int* d_bd = nullptr;
+};
+
+int fuse_batch_stage(Matcher& m, int nkf, const orbmi_frame_view* kfs, const DevFrame* frames, const orbmi_mappoint* mps,
+                     const uint8_t* in_kf, int n_mp, int32_t* best_idx, int32_t* best_dist, std::vector<OutBuf>& outs,
+                     FusePlan* P) {
+    int rc = 0;
+    std::vector<FuseKF> K(nkf);
+    P->d_mps = dev_in(m, mps, (size_t)n_mp, &rc);
+    const uint8_t* d_in = dev_in(m, in_kf, in_kf ? (size_t)std::max(n_mp, 1) * nkf : 0, &rc);
+    if (rc) return rc;
+    for (int k = 0; k < nkf; k++) {
+        memset(&K[k], 0, sizeof(FuseKF));
+        if (frames) K[k].F = frames[k];
+        else if ((rc = make_frame(m, &kfs[k], &K[k].F, true))) return rc;
+        K[k].in_kf = d_in ? d_in + (size_t)k * n_mp : nullptr;
+    }
+    P->nkf = nkf;
+    P->n = n_mp;
+    P->d_k = (FuseKF*)m.stage(sizeof(FuseKF) * nkf);
+    P->d_cnt = (int*)m.stage(sizeof(int) * nkf);
+    P->d_bi = dev_out(m, best_idx, (size_t)n_mp * nkf, outs);
+    P->d_bd = dev_out(m, best_dist, (size_t)n_mp * nkf, outs);
+    if (!P->d_k || !P->d_cnt) return ORBMI_E_HIP;
+    if ((rc = orbmi::fuse_multi_prepare(m, nkf, K.data(), n_mp, P->d_bi, P->d_bd, P->d_cnt, &P->ncap))) return rc;
+    ORBMI_HIP(m.h2d(P->d_k, K.data(), sizeof(FuseKF) * nkf));
+    return ORBMI_OK;
+}
+
+int fuse_batch_launch(Matcher& m, const FusePlan& P, float th) {
+    return orbmi::launch_fuse_multi(m, P.nkf, nullptr, P.d_k, P.d_mps, P.n, th, P.d_bi, P.d_bd, P.d_cnt, P.ncap);
+}
+
 }  // namespace
 
 extern "C" {
@@ -441,8 +582,15 @@ int orbmi_search_local_points_track(orbmi_matcher* h, const orbmi_frame_view* v,
     }
     int* d_out = dev_out(m, match_mp, (size_t)F.n, outs);
     // Tracking::SearchLocalPoints: isInFrustum(pMP, 0.5); ORBmatcher matcher(0.8)
+#ifdef ORBMI_FRUSTUM_SEPARATE  // A/B builds (ORBMI_CFLAGS): k_frustum as its own launch ahead of the search
     if ((rc = orbmi::launch_frustum(m, F, d_mps, n_mp, 0.5f, d_tr, n_to_match ? m.d_scalars + 1 : nullptr))) return rc;
     if ((rc = orbmi::launch_local_search(m, F, d_occ, d_mps, d_tr, n_mp, th, 0.8f, d_out, m.d_scalars))) return rc;
+#else
+    // (isInFrustum runs inside the search's candidate kernel, which writes d_tr)
+    if ((rc = orbmi::launch_local_search(m, F, d_occ, d_mps, d_tr, n_mp, th, 0.8f, d_out, m.d_scalars, d_tr, 0.5f,
+                                         n_to_match ? m.d_scalars + 1 : nullptr)))
+        return rc;
+#endif
     ORBMI_HIP(hipGetLastError());
     int ntm = 0;  // read back (and waited for) only when the caller asks for it
     rc = finish(m, outs, m.d_scalars, nmatches, m.d_scalars + 1, n_to_match ? &ntm : nullptr);
@@ -692,76 +840,15 @@ int orbmi_create_new_map_points(orbmi_matcher* h, const orbmi_frame_view* kf1, c
     Matcher& m = h->m;
     ORBMI_HIP(hipSetDevice(m.device));
     m.arena_reset();
-    DevFrame K1;
     DevFV f1;
     int rc;
-    if ((rc = make_frame(m, kf1, &K1, true))) return rc;
     if ((rc = make_fv(m, fv1, &f1))) return rc;
-    const size_t n1 = (size_t)std::max(K1.n, 1);
-    const uint8_t* has1 = dev_in(m, has_mp1, n1, &rc);
-    if (rc) return rc;
-    std::vector<std::vector<float>> cos_tmp;  // tables computed here, alive until the copies ran
-    cos_tmp.reserve((size_t)npairs + 1);
-    // the triangulation side of a keyframe: keys / u_right from its frame view (device), the rest
-    // from its tri view
-    auto side = [&](const orbmi_tri_keyframe* T, const orbmi_frame_view* v, const DevFrame& D, const float* cs,
-                    orbmi::tri::Side* S) -> int {
-        if (!T->tcw || !T->depth || !T->level_sigma2 || !T->scale_factors || on_device(T->level_sigma2) ||
-            on_device(T->scale_factors) || v->nlevels > orbmi::tri::kLevels)
-            return ORBMI_E_ARG;
-        orbmi::tri::make_side(*T, v->nlevels, S);
-        S->keys = D.keys;
-        S->ur = D.u_right;
-        int r = 0;
-        S->depth = dev_in(m, T->depth, (size_t)D.n, &r);
-        if (r) return r;
-        if (!cs) {
-            if (on_device(T->depth)) return ORBMI_E_ARG;
-            cos_tmp.emplace_back((size_t)std::max(D.n, 1));
-            if ((r = orbmi_stereo_parallax_cos(T->mb, T->depth, D.n, cos_tmp.back().data()))) return r;
-            cs = cos_tmp.back().data();
-        }
-        S->cos_stereo = dev_in(m, cs, (size_t)D.n, &r);
-        return r;
-    };
-    orbmi::tri::Side S1;
-    if ((rc = side(tri1, kf1, K1, cos1, &S1))) return rc;
-    std::vector<orbmi::tri::Side> S2(npairs);
-    std::vector<TriPair> pairs(npairs);
-    const bool F_dev = on_device(F12);
-    std::vector<float> Fh((size_t)9 * npairs);
-    if (F_dev) ORBMI_HIP(hipMemcpy(Fh.data(), F12, Fh.size() * sizeof(float), hipMemcpyDeviceToHost));
-    else memcpy(Fh.data(), F12, Fh.size() * sizeof(float));
-    for (int j = 0; j < npairs; j++) {
-        TriPair& P = pairs[j];
-        memset(&P, 0, sizeof(P));
-        if (!kf2[j].u_right || !has_mp2[j]) return ORBMI_E_ARG;
-        if ((rc = make_frame(m, &kf2[j], &P.KF2, true))) return rc;
-        if ((rc = make_fv(m, &fv2[j], &P.fv2))) return rc;
-        P.has_mp2 = dev_in(m, has_mp2[j], (size_t)std::max(P.KF2.n, 1), &rc);
-        if (rc) return rc;
-        for (int q = 0; q < 9; q++) P.F12.m[q] = Fh[9 * j + q];
-        if ((rc = side(&tri2[j], &kf2[j], P.KF2, cos2 ? cos2[j] : nullptr, &S2[j]))) return rc;
-    }
+    CnmpPlan P;
     std::vector<OutBuf> outs;
-    int* d_match = dev_out(m, match12, (size_t)K1.n * npairs, outs);
-    uint8_t* d_ok = dev_out(m, ok, (size_t)K1.n * npairs, outs);
-    float* d_x3d = dev_out(m, x3d, (size_t)3 * K1.n * npairs, outs);
-    if (!d_match || !d_ok || !d_x3d) return ORBMI_E_HIP;
-    if ((rc = orbmi::tri_pairs_prepare(m, K1, npairs, pairs.data(), d_match))) return rc;
-    // the pair table and the KF2 sides go up in one copy
-    const size_t o_s2 = (sizeof(TriPair) * npairs + 255) & ~(size_t)255;
-    const size_t tab_bytes = o_s2 + sizeof(orbmi::tri::Side) * npairs;
-    std::vector<uint8_t> tab(tab_bytes);
-    memcpy(tab.data(), pairs.data(), sizeof(TriPair) * npairs);
-    memcpy(tab.data() + o_s2, S2.data(), sizeof(orbmi::tri::Side) * npairs);
-    uint8_t* d_tab = (uint8_t*)m.stage(tab_bytes);
-    if (!d_tab) return ORBMI_E_HIP;
-    ORBMI_HIP(m.h2d(d_tab, tab.data(), tab_bytes));
-    TriPair* d_pairs = (TriPair*)d_tab;
-    const orbmi::tri::Side* d_S2 = (const orbmi::tri::Side*)(d_tab + o_s2);
-    if ((rc = orbmi::launch_create_points(m, K1, has1, f1, npairs, nullptr, d_pairs, S1, d_S2, d_match, d_ok, d_x3d)))
+    if ((rc = cnmp_stage(m, kf1, tri1, cos1, has_mp1, npairs, kf2, tri2, cos2, has_mp2, fv2, F12, match12, ok, x3d, outs,
+                         &P)))
         return rc;
+    if ((rc = cnmp_launch(m, P, f1))) return rc;
     return finish(m, outs, nullptr, nullptr);
 }
 
@@ -796,29 +883,17 @@ int orbmi_fuse_search_batch(orbmi_matcher* h, int nkf, const orbmi_frame_view* k
     ORBMI_HIP(hipSetDevice(m.device));
     m.arena_reset();
     int rc = 0;
-    std::vector<FuseKF> K(nkf);
-    const orbmi_mappoint* d_mps = dev_in(m, mps, (size_t)n_mp, &rc);
-    const uint8_t* d_in = dev_in(m, in_kf, in_kf ? (size_t)std::max(n_mp, 1) * nkf : 0, &rc);
-    if (rc) return rc;
-    for (int k = 0; k < nkf; k++) {
-        memset(&K[k], 0, sizeof(FuseKF));
-        if ((rc = make_frame(m, &kfs[k], &K[k].F, true))) return rc;
-        K[k].in_kf = d_in ? d_in + (size_t)k * n_mp : nullptr;
-    }
-    FuseKF* d_k = (FuseKF*)m.stage(sizeof(FuseKF) * nkf);
-    int* d_cnt = (int*)m.stage(sizeof(int) * nkf);
+    FusePlan P;
     std::vector<OutBuf> outs;
-    int* d_bi = dev_out(m, best_idx, (size_t)n_mp * nkf, outs);
-    int* d_bd = dev_out(m, best_dist, (size_t)n_mp * nkf, outs);
-    if (!d_k || !d_cnt) return ORBMI_E_HIP;
-    if ((rc = orbmi::launch_fuse_multi(m, nkf, K.data(), d_k, d_mps, n_mp, th, d_bi, d_bd, d_cnt))) return rc;
+    if ((rc = fuse_batch_stage(m, nkf, kfs, nullptr, mps, in_kf, n_mp, best_idx, best_dist, outs, &P))) return rc;
+    if ((rc = fuse_batch_launch(m, P, th))) return rc;
     bool wait = false;
     ORBMI_HIP(m.flush_up());
     if (m.up_err != hipSuccess) return ORBMI_E_HIP;
     for (OutBuf& o : outs)
         if (o.bytes) { ORBMI_HIP(m.d2h(o.user, o.dev, o.bytes)); wait = true; }
     if (ncandidates) {
-        ORBMI_HIP(m.d2h(ncandidates, d_cnt, sizeof(int) * nkf));
+        ORBMI_HIP(m.d2h(ncandidates, P.d_cnt, sizeof(int) * nkf));
         wait = true;
     }
     if (wait) ORBMI_HIP(hipStreamSynchronize(m.ls()));
@@ -883,6 +958,112 @@ int orbmi_fuse_search_refresh(orbmi_matcher* h, const uint8_t* obs_desc, const i
         if ((rc = orbmi::launch_fuse_multi(m, nkf, K.data(), d_k, d_mps, n_mp, th, d_bi, d_bd, d_cnt))) return rc;
     }
     return finish(m, outs, nullptr, nullptr);
+}
+
+int orbmi_local_mapping_job(orbmi_matcher* h, orbmi_ba* ba, const orbmi_lm_job* J, orbmi_lm_job_result* R) {
+    if (!h || !ba || !J || !R) return ORBMI_E_ARG;
+    R->bow_words = R->fv_nodes = 0;
+    R->failed_stage = -1;
+    auto fail = [R](int stage, int rc) { R->failed_stage = stage; return rc; };
+    const int np = J->n_points, nnb = J->nnb, n_kp = J->n_kf_points, n_tp = J->n_target_points;
+    if (!J->kf || !J->problem || !J->result || !J->counts_host || !J->counts_event || !J->fv_node || !J->fv_off ||
+        !J->fv_feat || np < 0 || nnb < 0 || n_kp < 0 || n_tp < 0 || (np > 0 && (!J->obs_off || !J->best || !J->desc_out)) ||
+        (nnb > 0 && n_kp > 0 && (!J->kf_points || !J->best_idx || !J->best_dist)) ||
+        (n_tp > 0 && (!J->target_points || !J->best_idx || !J->best_dist)))
+        return ORBMI_E_ARG;
+    if (J->voc && (J->bow_n < 0 || !J->bow_counts || !J->bow_word || !J->bow_value)) return fail(0, ORBMI_E_ARG);
+    Matcher& m = h->m;
+    ORBMI_HIP(hipSetDevice(m.device));
+    m.arena_reset();  // the job's one arena generation
+    // an error leaves nothing pending in the arena: staged uploads and read-backs are dropped
+    struct Pending {
+        Matcher& m;
+        bool done = false;
+        ~Pending() {
+            if (!done) { m.up = Matcher::PendUp{}; m.pend.clear(); }
+        }
+    } pending{m};
+    auto mark = [&](int k) {  // a stage boundary for the caller's timeline (diagnostics)
+        if (J->stage_events && J->stage_events[k]) (void)hipEventRecord((hipEvent_t)J->stage_events[k], m.ls());
+    };
+    int rc;
+    // ---- ProcessNewKeyFrame: ComputeBoW (unless issued ahead) + ComputeDistinctiveDescriptors
+    hipEvent_t counts_ev = (hipEvent_t)J->counts_event;
+    if (J->voc) {
+        if ((rc = orbmi_transform(J->voc, J->bow_desc, J->bow_n, nullptr, 4, J->bow_word, J->bow_value, J->fv_node,
+                                  J->fv_off, J->fv_feat, J->bow_counts)))
+            return fail(0, rc);
+        void* vs = nullptr;
+        if ((rc = orbmi_vocabulary_get_stream(J->voc, &vs))) return fail(0, rc);
+        if ((hipStream_t)vs != m.stream && (rc = orbmi_vocabulary_synchronize(J->voc))) return fail(0, rc);
+        if (hipMemcpyAsync(const_cast<int32_t*>(J->counts_host), J->bow_counts, 2 * sizeof(int), hipMemcpyDeviceToHost,
+                           m.stream) != hipSuccess ||
+            hipEventRecord(counts_ev, m.stream) != hipSuccess)
+            return fail(0, ORBMI_E_HIP);
+    }
+    // enqueued first, so the stream is busy while the host builds the searches' tables
+    const uint8_t* d_obs = nullptr;
+    const int* d_off = nullptr;
+    std::vector<OutBuf> outs;
+    int* d_best = nullptr;
+    uint8_t* d_dsc = nullptr;
+    if (np > 0) {
+        if (!on_device(J->obs_desc) && J->obs_desc) return fail(1, ORBMI_E_ARG);  // (its row count is not read back here)
+        rc = 0;
+        d_obs = J->obs_desc;
+        d_off = dev_in(m, J->obs_off, (size_t)np + 1, &rc);
+        if (rc) return fail(1, rc);
+        d_best = dev_out(m, J->best, (size_t)np, outs);
+        d_dsc = dev_out(m, J->desc_out, (size_t)np * 32, outs);
+        if (!on_device(J->desc_out) && hipSuccess != m.h2d(d_dsc, J->desc_out, (size_t)np * 32)) return fail(1, ORBMI_E_HIP);
+        if ((rc = orbmi::launch_distinctive(m, d_obs, d_off, np, d_best, d_dsc))) return fail(1, rc);
+    }
+    mark(0);
+    // ---- every search's host tables: validated, built and staged now, one upload
+    CnmpPlan cn;
+    FusePlan fb;
+    DevFrame KF;
+    if (nnb > 0) {
+        if ((rc = cnmp_stage(m, J->kf, J->tri, J->cos, J->has_mp, nnb, J->kf2, J->tri2, J->cos2, J->has_mp2, J->fv2, J->F12,
+                             J->match12, J->ok, J->x3d, outs, &cn)))
+            return fail(2, rc);
+        if ((rc = fuse_batch_stage(m, nnb, J->kf2, cn.KF2.data(), J->kf_points, nullptr, n_kp, J->best_idx, J->best_dist,
+                                   outs, &fb)))
+            return fail(3, rc);
+        KF = cn.K1;
+    } else if ((rc = make_frame(m, J->kf, &KF, true))) {
+        return fail(3, rc);
+    }
+    const size_t o = (size_t)nnb * n_kp;  // Fuse(keyframe, targets' points) behind the targets' rows
+    rc = 0;
+    const orbmi_mappoint* d_tp = dev_in(m, J->target_points, (size_t)n_tp, &rc);
+    if (rc) return fail(3, rc);
+    int* d_bi = dev_out(m, J->best_idx ? J->best_idx + o : nullptr, (size_t)n_tp, outs);
+    int* d_bd = dev_out(m, J->best_dist ? J->best_dist + o : nullptr, (size_t)n_tp, outs);
+    // ---- the FeatureVector's node count sizes SearchForTriangulation: the one host wait ahead of LocalBA
+    if (hipEventSynchronize(counts_ev) != hipSuccess) return fail(0, ORBMI_E_HIP);
+    const int nw = J->counts_host[0], nn = J->counts_host[1];
+    if (nw < 0 || nn < 0) return fail(0, ORBMI_E_STATE);
+    R->bow_words = nw;
+    R->fv_nodes = nn;
+    // ---- CreateNewMapPoints
+    if (nnb > 0) {
+        const DevFV f1{nn, nn ? J->fv_node : nullptr, nn ? J->fv_off : nullptr, nn ? J->fv_feat : nullptr};
+        if ((rc = cnmp_launch(m, cn, f1))) return fail(2, rc);
+    }
+    mark(1);
+    // ---- SearchInNeighbors: Fuse(target, keyframe's points) per target, Fuse(keyframe, targets' points)
+    if (nnb > 0 && (rc = fuse_batch_launch(m, fb, J->fuse_th))) return fail(3, rc);
+    if ((rc = orbmi::launch_fuse(m, KF, d_tp, nullptr, n_tp, J->fuse_th, d_bi, d_bd, nullptr))) return fail(3, rc);
+    mark(2);
+    // ---- ComputeDistinctiveDescriptors of the keyframe's points after fusion
+    if (np > 0 && (rc = orbmi::launch_distinctive(m, d_obs, d_off, np, d_best, d_dsc))) return fail(4, rc);
+    mark(3);
+    if ((rc = finish(m, outs, nullptr, nullptr))) return fail(4, rc);
+    pending.done = true;
+    // ---- LocalBundleAdjustment (in stream order behind the searches when ba runs on this stream)
+    if ((rc = orbmi_local_bundle_adjustment(ba, J->problem, J->result, J->stop))) return fail(5, rc);
+    return ORBMI_OK;
 }
 
 int orbmi_debug_greedy_stats(unsigned long long* out, int reset) {

@@ -2541,6 +2541,12 @@ struct orbmi_ba {
     uint8_t* h_stage = nullptr;  // pinned staging of the uploaded graph (one H2D copy)
     size_t cap_stage = 0;
     hipEvent_t up_done = nullptr;  // the last upload from h_stage has been read
+    // the graph upload's own stream (created at the first call): the copy depends on nothing
+    // enqueued ahead of LocalBA on `stream` (a LocalMapping chain's searches), so it runs beside
+    // that work and `stream` waits for up_done only.  ORBMI_BA_UPLOAD=inline keeps the copy in
+    // stream order (A/B runs)
+    hipStream_t up_stream = nullptr;
+    bool up_beside = true;
     uint8_t* h_out = nullptr;      // pinned staging of the results (poses, positions, erase flags)
     size_t cap_out = 0;
     orbmi::BaCtl* h_ctl = nullptr;  // pinned readback of the LM control block
@@ -2742,6 +2748,8 @@ int orbmi_ba_create(int device, orbmi_ba** out) {
         return ORBMI_E_HIP;
     }
     *b->h_stop = 0;
+    const char* up_env = getenv("ORBMI_BA_UPLOAD");
+    b->up_beside = !(up_env && !strcmp(up_env, "inline"));
     *out = b;
     return ORBMI_OK;
 }
@@ -2755,6 +2763,10 @@ void orbmi_ba_destroy(orbmi_ba* b) {
     if (b->h_ctl) (void)hipHostFree(b->h_ctl);
     if (b->h_stop) (void)hipHostFree(b->h_stop);
     if (b->done) (void)hipEventDestroy(b->done);
+    if (b->up_stream) {
+        (void)hipStreamSynchronize(b->up_stream);
+        (void)hipStreamDestroy(b->up_stream);
+    }
     if (b->up_done) (void)hipEventDestroy(b->up_done);
     if (b->h_out) (void)hipHostFree(b->h_out);
     if (b->stream && b->own_stream) (void)hipStreamDestroy(b->stream);
@@ -2946,8 +2958,15 @@ int orbmi_local_bundle_adjustment(orbmi_ba* b, const orbmi_ba_problem* P, orbmi_
     }
     uint8_t* B = h.d_buf;
     tr.mark("host_index");
-    ORBMI_HIP(hipMemcpyAsync(B, S, up_bytes, hipMemcpyHostToDevice, s));
-    ORBMI_HIP(hipEventRecord(h.up_done, s));
+    // (the arena's previous reader, the last call's solve, finished before that call returned)
+    hipStream_t us = s;
+    if (h.up_beside) {
+        if (!h.up_stream) ORBMI_HIP(orbmi::stream_create(&h.up_stream, "BA"));
+        us = h.up_stream;
+    }
+    ORBMI_HIP(hipMemcpyAsync(B, S, up_bytes, hipMemcpyHostToDevice, us));
+    ORBMI_HIP(hipEventRecord(h.up_done, us));
+    if (us != s) ORBMI_HIP(hipStreamWaitEvent(s, h.up_done, 0));
     const size_t out_bytes = o_oerase + (size_t)std::max(ne, 1) - o_otcw;  // tcw, pos, erase (aligned)
     if (out_bytes > h.cap_out) {
         if (h.h_out) (void)hipHostFree(h.h_out);

@@ -160,7 +160,8 @@ int pin_grid_slot(Matcher& m, const DevFrame& F, int k);
 int launch_frustum(Matcher& m, const DevFrame& F, const orbmi_mappoint* mps, int n, float cosl,
                    orbmi_mappoint_track* tr, int* n_in_view);
 int launch_local_search(Matcher& m, const DevFrame& F, const uint8_t* occ0, const orbmi_mappoint* mps,
-                        const orbmi_mappoint_track* tr, int n, float th, float nnratio, int* out, int* nmatches);
+                        const orbmi_mappoint_track* tr, int n, float th, float nnratio, int* out, int* nmatches,
+                        orbmi_mappoint_track* tr_fused = nullptr, float frustum_cos = 0.f, int* n_in_view = nullptr);
 int launch_lastframe_search(Matcher& m, const DevFrame& CF, const uint8_t* occ0, const DevFrame& LF,
                             const orbmi_lastframe_point* lfp, float th, int mono, int check_ori, int* out,
                             int* nmatches, const int* gate = nullptr, int gate_min = 0);
@@ -179,8 +180,11 @@ int launch_create_points(Matcher& m, const DevFrame& KF1, const uint8_t* has1, c
                          int* match, uint8_t* ok, float* x3d);
 int launch_fuse(Matcher& m, const DevFrame& F, const orbmi_mappoint* mps, const uint8_t* in_kf, int n, float th,
                 int* best_idx, int* best_dist, int* ncand);
+int fuse_multi_prepare(Matcher& m, int nkf, FuseKF* kfs_host, int n, int* best_idx, int* best_dist, int* ncand,
+                       int* ncap_out);
+// kfs_host == nullptr: the table is already prepared (fuse_multi_prepare -> ncap) and uploaded
 int launch_fuse_multi(Matcher& m, int nkf, FuseKF* kfs_host, FuseKF* kfs_dev, const orbmi_mappoint* mps, int n,
-                      float th, int* best_idx, int* best_dist, int* ncand);
+                      float th, int* best_idx, int* best_dist, int* ncand, int ncap = 0);
 int launch_patch_desc(Matcher& m, orbmi_mappoint* mps, const int* desc_from, const uint8_t* desc, int n);
 int greedy_stats(unsigned long long out[5], int reset);
 int greedy_cycles(unsigned long long out[7], int reset);

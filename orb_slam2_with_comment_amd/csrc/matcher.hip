@@ -136,16 +136,14 @@ __device__ inline void camera_center(const float* T, float* o) {
 }
 
 // -------------------------------------------------------------------------- frustum
-__global__ __launch_bounds__(256) void k_frustum(DevFrame F, const orbmi_mappoint* __restrict__ mps, int n,
-                                                 float viewingCosLimit, orbmi_mappoint_track* __restrict__ tr,
-                                                 int* __restrict__ n_in_view) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
+// Frame::isInFrustum (src/Frame.cc:296-353) of one map point at pose T: its track record.  The
+// standalone kernel and the local-map candidate kernel both run this one sequence of operations
+// (one rounding each, -ffp-contract=off), so their records agree bit for bit.
+__device__ inline orbmi_mappoint_track frustum_record(const DevFrame& F, const Pose34& T, const orbmi_mappoint& mp,
+                                                      float viewingCosLimit) {
     orbmi_mappoint_track t = {0, 0.f, 0.f, 0.f, 0, 0.f};
-    const orbmi_mappoint mp = mps[i];
     bool ok = !(mp.flags & (ORBMI_MP_BAD | ORBMI_MP_SEEN));
     float Pc[3], Ow[3], u = 0, v = 0, invz = 0, dist = 0, viewCos = 0;
-    const Pose34 T = frame_pose(F);
     if (ok) {
         transform(T.m, mp.pos, Pc);
         ok = !(Pc[2] < 0.0f);
@@ -179,8 +177,19 @@ __global__ __launch_bounds__(256) void k_frustum(DevFrame F, const orbmi_mappoin
         t.proj_y = v;
         t.level = nScale;
         t.view_cos = viewCos;
-        if (n_in_view) atomicAdd(n_in_view, 1);
     }
+    return t;
+}
+
+__global__ __launch_bounds__(256) void k_frustum(DevFrame F, const orbmi_mappoint* __restrict__ mps, int n,
+                                                 float viewingCosLimit, orbmi_mappoint_track* __restrict__ tr,
+                                                 int* __restrict__ n_in_view) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const orbmi_mappoint mp = mps[i];
+    const Pose34 T = frame_pose(F);
+    const orbmi_mappoint_track t = frustum_record(F, T, mp, viewingCosLimit);
+    if (t.in_view && n_in_view) atomicAdd(n_in_view, 1);
     tr[i] = t;
 }
 
@@ -283,6 +292,11 @@ struct CandArgs {
     const int* cl;
     const orbmi_mappoint* mps;
     const orbmi_mappoint_track* tr;
+    // k_candidates<G, true> (mode 0): isInFrustum runs here; every point's record goes to tr_out
+    // (k_greedy and the caller read it) and the points in view are counted into n_in_view (optional)
+    orbmi_mappoint_track* tr_out;
+    float frustum_cos;
+    int* n_in_view;
     const orbmi_lastframe_point* lfp;
     float th;
     int mono;
@@ -299,18 +313,19 @@ struct Window {
     const uint8_t* desc;
 };
 
+__device__ inline bool local_window(const CandArgs& a, const orbmi_mappoint& mp, const orbmi_mappoint_track& t,
+                                    Window* w) {
+    int level;
+    if (!local_query(a.F, mp, t, a.th, &w->x, &w->y, &w->r, &level)) return false;
+    w->minL = level - 1;
+    w->maxL = level;
+    w->ur = t.proj_xr;
+    w->desc = mp.desc;
+    return true;
+}
+
 __device__ inline bool make_window(const CandArgs& a, int q, const float* Tc, bool fw, bool bw, Window* w) {
-    if (a.mode == 0) {
-        const orbmi_mappoint& mp = a.mps[q];
-        const orbmi_mappoint_track t = a.tr[q];
-        int level;
-        if (!local_query(a.F, mp, t, a.th, &w->x, &w->y, &w->r, &level)) return false;
-        w->minL = level - 1;
-        w->maxL = level;
-        w->ur = t.proj_xr;
-        w->desc = mp.desc;
-        return true;
-    }
+    if (a.mode == 0) return local_window(a, a.mps[q], a.tr[q], w);
     const orbmi_lastframe_point& p = a.lfp[q];
     LfQuery lq;
     if (!lf_query(a.F, Tc, a.LF, p, q, a.th, fw, bw, &lq)) return false;
@@ -319,7 +334,9 @@ __device__ inline bool make_window(const CandArgs& a, int q, const float* Tc, bo
     return true;
 }
 
-template <int G>
+// FR (mode 0 only): the group first computes its point's isInFrustum record (every lane the same
+// operations; lane 0 stores it), in place of a k_frustum launch ahead of this one
+template <int G, bool FR = false>
 __global__ __launch_bounds__(256) void k_candidates(CandArgs a) {
     constexpr int NG = 256 / G, cap = Matcher::kCandCap;
     __shared__ unsigned long long buf[NG][cap];
@@ -335,7 +352,21 @@ __global__ __launch_bounds__(256) void k_candidates(CandArgs a) {
         motion_direction(a.F, Tc.m, a.LF, a.mono, &fw, &bw);
     }
     Window w;
-    const bool valid = q < nq && make_window(a, q, Tc.m, fw, bw, &w);
+    bool valid = false;
+    if constexpr (FR) {
+        if (q < nq) {
+            const orbmi_mappoint& mp = a.mps[q];
+            const Pose34 T = frame_pose(a.F);
+            const orbmi_mappoint_track t = frustum_record(a.F, T, mp, a.frustum_cos);
+            if (lane == 0) {
+                a.tr_out[q] = t;
+                if (t.in_view && a.n_in_view) atomicAdd(a.n_in_view, 1);
+            }
+            valid = local_window(a, mp, t, &w);
+        }
+    } else {
+        valid = q < nq && make_window(a, q, Tc.m, fw, bw, &w);
+    }
     if (lane == 0) cnt[gl] = 0;
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
@@ -1243,8 +1274,11 @@ int launch_frustum(Matcher& m, const DevFrame& F, const orbmi_mappoint* mps, int
     return ORBMI_OK;
 }
 
+// tr_fused (== tr, or nullptr): isInFrustum(frustum_cos) runs inside the candidate kernel, which
+// writes the n records there and counts the points in view into n_in_view (may be nullptr)
 int launch_local_search(Matcher& m, const DevFrame& F, const uint8_t* occ0, const orbmi_mappoint* mps,
-                        const orbmi_mappoint_track* tr, int n, float th, float nnratio, int* out, int* nmatches) {
+                        const orbmi_mappoint_track* tr, int n, float th, float nnratio, int* out, int* nmatches,
+                        orbmi_mappoint_track* tr_fused, float frustum_cos, int* n_in_view) {
     if (n >= kGreedyMaxQueries) return ORBMI_E_UNSUPPORTED;  // k_greedy's claim field
     int rc;
     if ((rc = grid_for(m, F))) return rc;
@@ -1257,7 +1291,12 @@ int launch_local_search(Matcher& m, const DevFrame& F, const uint8_t* occ0, cons
         CandArgs ca{};
         ca.mode = 0; ca.nq = n; ca.F = F; ca.cs = m.cur_cs; ca.cl = m.cur_cl; ca.mps = mps; ca.tr = tr;
         ca.th = th; ca.cand = m.d_cand; ca.ncand = m.d_ncand; ca.top = m.d_top;
-        hipLaunchKernelGGL(k_candidates<16>, dim3((n + 15) / 16), dim3(256), 0, m.ls(), ca);
+        if (tr_fused) {
+            ca.tr_out = tr_fused; ca.frustum_cos = frustum_cos; ca.n_in_view = n_in_view;
+            hipLaunchKernelGGL((k_candidates<16, true>), dim3((n + 15) / 16), dim3(256), 0, m.ls(), ca);
+        } else {
+            hipLaunchKernelGGL(k_candidates<16>, dim3((n + 15) / 16), dim3(256), 0, m.ls(), ca);
+        }
     }
     GreedyArgs a{};
     a.mode = 0; a.nq = n; a.cand = m.d_cand; a.ncand = m.d_ncand; a.top = m.d_top; a.cap = cap; a.occ0 = occ0; a.F = F;
@@ -1831,9 +1870,10 @@ int launch_fuse(Matcher& m, const DevFrame& F, const orbmi_mappoint* mps, const 
     return hipGetLastError() == hipSuccess ? ORBMI_OK : ORBMI_E_HIP;
 }
 
-int launch_fuse_multi(Matcher& m, int nkf, FuseKF* kfs_host, FuseKF* kfs_dev, const orbmi_mappoint* mps, int n,
-                      float th, int* best_idx, int* best_dist, int* ncand) {
-    if (nkf <= 0) return ORBMI_OK;
+// the keyframes' grids and output rows of a batched Fuse search, filled into the host table
+// (keyframe k's results at best_idx / best_dist + k * n); *ncap_out = the grids' row length
+int fuse_multi_prepare(Matcher& m, int nkf, FuseKF* kfs_host, int n, int* best_idx, int* best_dist, int* ncand,
+                       int* ncap_out) {
     int ncap = 1;
     for (int k = 0; k < nkf; k++) {
         if (kfs_host[k].F.n > kGreedyMaxKp) return ORBMI_E_UNSUPPORTED;
@@ -1851,7 +1891,19 @@ int launch_fuse_multi(Matcher& m, int nkf, FuseKF* kfs_host, FuseKF* kfs_dev, co
         K.best_dist = best_dist + (size_t)k * n;
         K.ncand = ncand + k;
     }
-    ORBMI_HIP(m.h2d(kfs_dev, kfs_host, sizeof(FuseKF) * nkf));
+    *ncap_out = ncap;
+    return ORBMI_OK;
+}
+
+// kfs_host == nullptr: the caller prepared (fuse_multi_prepare -> ncap) and uploaded the table
+int launch_fuse_multi(Matcher& m, int nkf, FuseKF* kfs_host, FuseKF* kfs_dev, const orbmi_mappoint* mps, int n,
+                      float th, int* best_idx, int* best_dist, int* ncand, int ncap) {
+    if (nkf <= 0) return ORBMI_OK;
+    if (kfs_host) {
+        int rc;
+        if ((rc = fuse_multi_prepare(m, nkf, kfs_host, n, best_idx, best_dist, ncand, &ncap))) return rc;
+        ORBMI_HIP(m.h2d(kfs_dev, kfs_host, sizeof(FuseKF) * nkf));
+    }
     hipLaunchKernelGGL(k_grid_build_multi, dim3(nkf), dim3(1024), 0, m.ls(), kfs_dev, m.d_mkp_cell, ncap);
     if (n > 0)
         hipLaunchKernelGGL(k_fuse_multi, dim3((n * kFuseLanes + 255) / 256, nkf), dim3(256), 0, m.ls(), kfs_dev, mps, n,

@@ -44,6 +44,11 @@ class LocalBA:
         check("orbmi_local_bundle_adjustment",
               lib().orbmi_local_bundle_adjustment(self._h, C.addressof(v), C.addressof(r),
                                                   C.addressof(stop) if stop is not None else None))
+        return self.result(problem, r, tcw, pos, erase)
+
+    @staticmethod
+    def result(problem: BAProblem, r, tcw, pos, erase):
+        """run()'s return value from a filled orbmi_ba_result and its buffers (problem.result_buffers())."""
         n = len(problem.kfs), len(problem.pts), len(problem.edges)
         return {"tcw": tcw[:n[0]].reshape(-1, 4, 4), "pos": pos[:n[1]], "erase": erase[:n[2]].astype(bool),
                 "iterations": tuple(r.iterations), "chi2": tuple(r.chi2), "aborted": r.aborted,

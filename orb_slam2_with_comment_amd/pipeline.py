@@ -82,12 +82,12 @@ class StereoTracker:
         from .types import POSE_FRAME_DTYPE
         self.cam, self.device, self.pipelined = cam, device, pipelined
         self.unfused = os.environ.get("ORBMI_TRACK_UNFUSED") == "1"  # A/B: pose and update as two launches
-        # ORBMI_GRID_AHEAD=1 (pipelined): Frame::AssignFeaturesToGrid on the extraction stream
-        # right after the frame's keypoints (a slot grid per frame slot), off the tracking chain.
-        # Tracking alone gains 3.5 % (0.319 -> 0.308 ms per frame back to back), but the headline
-        # with the concurrent LocalMapping chain loses 2.7 % (profiles/r06/grid_ahead_ab.txt), so
-        # the default builds the grid on the tracking stream at the first search
-        self.grid_ahead = pipelined and os.environ.get("ORBMI_GRID_AHEAD", "0") == "1"
+        # Frame::AssignFeaturesToGrid on the extraction stream right after the frame's keypoints (a
+        # slot grid per frame slot), off the tracking chain: 6.7 us less per frame on the tracking
+        # stream, and with the LocalMapping job as one native call (whose chain no longer bounds
+        # the headline) +1 % on the headline.  ORBMI_GRID_AHEAD=0 builds the grid on
+        # the tracking stream at the first search (pipelined trackers only have the choice)
+        self.grid_ahead = pipelined and os.environ.get("ORBMI_GRID_AHEAD", "1") == "1"
         self._tcw0 = np.eye(4, dtype=np.float32)  # (the grid reads no pose)
         self.frame_events = None  # a list: per-frame [extract start, end, track start, end] events (pipelined)
         self.extractor = ORBextractor(nfeatures, scale_factor, nlevels, ini_th, min_th, device=device)
@@ -180,9 +180,13 @@ class StereoTracker:
             self.extractor.handle, self.cam.bf, self.cam.fx, _vp(sl["u_right"].data_ptr()), _vp(sl["depth"].data_ptr())))
         # new keypoints behind the slot's pointers: a grid pinned on an earlier frame is stale
         check("orbmi_matcher_release_grid", L.orbmi_matcher_release_grid(self.matcher._h))
-        if self.grid_ahead and slot is not None:
+        if self.grid_ahead:
             # the slot's grid, in stream order behind its keypoints; the searches read it behind the
-            # extraction event, and the slot's next extraction waits for them (_ev_tracked)
+            # extraction event, and the slot's next extraction waits for them (_ev_tracked).  (A
+            # caller that drives the stages itself extracts into the current slot and orders the
+            # tracking stream behind this one, as track() does.)
+            if slot is None:
+                slot = self.slot
             v = frame_view(self.cap, sl["kps"].data_ptr(), sl["u_right"].data_ptr(), sl["desc"].data_ptr(), self._tcw0,
                            self.cam, self.scale_factors, self.cam.width, self.cam.height,
                            n_device=sl["counts"].data_ptr())
@@ -409,6 +413,22 @@ class LocalMappingJob:
         self.c_fv2 = (FeatureVectorView * max(nnb, 1))(*[nb.fv_dev if nb.fv_dev is not None else nb.fv.view()
                                                           for nb in neighbours])
         self.c_F12 = np.ascontiguousarray(np.concatenate(self.F12) if nnb else np.zeros(9), np.float32)
+        # orbmi_lm_job with the fields that belong to the job filled in (marshalling only: the
+        # call validates and builds everything from them each time); LocalMapper.run_job adds the
+        # BowVector / FeatureVector set, its output buffers and the LocalBA result
+        from .types import LMJob
+        c = self.c_job = LMJob()
+        c.bow_desc, c.bow_n = d_desc, kf.n
+        c.obs_desc, c.obs_off, c.n_points = obs[0], obs[1], int(obs[2])
+        c.kf, c.tri = C.addressof(kf.view), C.addressof(kf.tri_dev)
+        c.cos, c.has_mp = kf.d_cos.data_ptr(), kf.d_has_mp
+        c.nnb = nnb
+        c.kf2, c.tri2 = C.addressof(self.c_kf2), C.addressof(self.c_tri2)
+        c.cos2, c.has_mp2 = C.addressof(self.c_cos2), C.addressof(self.c_mp2)
+        c.fv2, c.F12 = C.addressof(self.c_fv2), self.c_F12.ctypes.data
+        c.kf_points, c.n_kf_points = kf_points[0], int(kf_points[1])
+        c.target_points, c.n_target_points = target_points[0], int(target_points[1])
+        c.fuse_th = 3.0
 
 
 class ChainStats(dict):
@@ -508,6 +528,11 @@ class LocalMapper:
         # streams stay within the device's hardware queues (orbmi_ba_set_stream); without the
         # transform ahead, ComputeBoW joins them there
         self._one_stream = os.environ.get("ORBMI_LM_STREAMS", "one") == "one"
+        # a LocalMappingJob runs as one native call (orbmi_local_mapping_job); ORBMI_LM_NATIVE=0
+        # keeps the call-by-call chain (A/B runs, and the comparator of the native job's test).  A
+        # library build named by ORBMI_LIB that predates the entry (A/B timing) runs call by call
+        self._native = os.environ.get("ORBMI_LM_NATIVE", "1") != "0" and (
+            not os.environ.get("ORBMI_LIB") or hasattr(lib(), "orbmi_local_mapping_job"))
         if self._one_stream:
             check("orbmi_ba_set_stream", lib().orbmi_ba_set_stream(self.ba._h, ms))
             if vocabulary is not None and not self._prebow:
@@ -535,12 +560,13 @@ class LocalMapper:
         self.t = threading.Thread(target=self._run, daemon=True)
         self.t.start()
 
-    def _buf(self, name, shape, dtype):
+    def _buf(self, name, n, dtype):
+        """The chain's output buffer `name` with room for n elements (kept from job to job)."""
         import torch
         b = self._bufs.get(name)
-        if b is None or b.numel() < int(np.prod(shape)) or b.dtype != dtype:
+        if b is None or b.numel() < n or b.dtype != dtype:
             with torch.cuda.stream(self._ms):  # allocated on the stream that writes it
-                b = torch.empty(int(np.prod(shape)), dtype=dtype, device=self._dev)
+                b = torch.empty(int(n), dtype=dtype, device=self._dev)
             self._bufs[name] = b
         return b
 
@@ -580,11 +606,18 @@ class LocalMapper:
         CreateNewMapPoints (the FeatureVector's node count sizes its search) and the one LocalBA
         ends with; the statistics of the searches are read lazily (ChainStats)."""
         import torch
-        from .types import FeatureVector, FeatureVectorView
+        from .types import FeatureVector
         L = lib()
         m = self.matcher._h
         kf = job.kf
         je = self.job_events  # diagnostics (bench --frame-events): the job's span on the stream
+        native = self._native
+        if je is not None and native:
+            # the stage boundaries are recorded inside the call: events that exist already (a torch
+            # event gets its handle at its first record), outside the job's span
+            stage_ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
+            for ev in stage_ev:
+                ev.record(self._ms)
         if je is not None:
             t_host0 = time.perf_counter()
             e0 = torch.cuda.Event(enable_timing=True)
@@ -608,16 +641,17 @@ class LocalMapper:
             self.bow = b
         else:  # enqueued back to back with ComputeDistinctiveDescriptors
             b, counts_h = self.bow, self._counts_h
-            self.voc.transform_device(job.d_desc, kf.n, None, 4, b["word"].data_ptr(), b["value"].data_ptr(),
-                                      b["node"].data_ptr(), b["off"].data_ptr(), b["feat"].data_ptr(),
-                                      b["counts"].data_ptr())
-            if not self._one_stream:  # the transform ran on the vocabulary's own stream
-                self.voc.synchronize()
-            # mBowVec / mFeatVec sizes, behind the transform on the mapper's stream
-            counts_h.copy_async(b["counts"].data_ptr(), self._ms.cuda_stream)
+            if not native:  # (the native call issues the transform and its size copy itself)
+                self.voc.transform_device(job.d_desc, kf.n, None, 4, b["word"].data_ptr(), b["value"].data_ptr(),
+                                          b["node"].data_ptr(), b["off"].data_ptr(), b["feat"].data_ptr(),
+                                          b["counts"].data_ptr())
+                if not self._one_stream:  # the transform ran on the vocabulary's own stream
+                    self.voc.synchronize()
+                # mBowVec / mFeatVec sizes, behind the transform on the mapper's stream
+                counts_h.copy_async(b["counts"].data_ptr(), self._ms.cuda_stream)
         d_obs, d_off, npts = job.obs
-        best = self._buf("best", (max(npts, 1),), torch.int32)
-        dsc = self._buf("dsc", (max(npts, 1) * 32,), torch.uint8)
+        best = self._buf("best", max(npts, 1), torch.int32)
+        dsc = self._buf("dsc", max(npts, 1) * 32, torch.uint8)
 
         def distinctive():
             check("orbmi_compute_distinctive_descriptors", L.orbmi_compute_distinctive_descriptors(
@@ -625,49 +659,26 @@ class LocalMapper:
         # enqueued first, so the stream is busy while the host prepares CreateNewMapPoints (putting
         # CreateNewMapPoints first left the stream idle for that setup: 2,836-2,881 against
         # 2,914-2,949 frames/s, profiles/r06/lm_prebow_ab.txt)
-        distinctive()
+        if not native:
+            distinctive()
         # the later stages' buffers, prepared while the GPU runs the calls above
         nnb = len(job.neighbours)
-        tri = self._buf("tri", (max(nnb, 1) * kf.n,), torch.int32)
-        tri_ok = self._buf("tri_ok", (max(nnb, 1) * kf.n,), torch.uint8)
-        x3d = self._buf("tri_x3d", (max(nnb, 1) * kf.n * 3,), torch.float32)
+        tri = self._buf("tri", max(nnb, 1) * kf.n, torch.int32)
+        tri_ok = self._buf("tri_ok", max(nnb, 1) * kf.n, torch.uint8)
+        x3d = self._buf("tri_x3d", max(nnb, 1) * kf.n * 3, torch.float32)
         d_kp, n_kp = job.kf_points
         d_tp, n_tp = job.target_points
-        bi = self._buf("fuse_bi", (max(nnb * n_kp + n_tp, 1),), torch.int32)
-        bd = self._buf("fuse_bd", (max(nnb * n_kp + n_tp, 1),), torch.int32)
-        kf2 = job.c_kf2
-        mark("bow_distinctive")
-        # waits for the size copy only (whatever the stream mode).  With the transform ahead the
-        # copy follows the transform on the vocabulary's stream, so once the host has read the
-        # sizes the FeatureVector is complete too and the mapper's stream needs no cross-stream
-        # wait (a wait packet costs the stream ~10 us)
-        nw, nn = counts_h.read()
-        # ---- CreateNewMapPoints: every neighbour's SearchForTriangulation and the triangulation /
-        # acceptance geometry on the device, in the reference's pair order (orbmi_create_new_map_points)
-        fv1 = FeatureVectorView(nn, b["node"].data_ptr(), b["off"].data_ptr(), b["feat"].data_ptr())
-        if nnb:
-            check("orbmi_create_new_map_points", L.orbmi_create_new_map_points(
-                m, C.addressof(kf.view), C.addressof(kf.tri_dev), _vp(kf.d_cos.data_ptr()), _vp(kf.d_has_mp),
-                C.addressof(fv1), nnb, kf2, job.c_tri2, job.c_cos2, job.c_mp2, job.c_fv2, job.c_F12.ctypes.data,
-                _vp(tri.data_ptr()), _vp(tri_ok.data_ptr()), _vp(x3d.data_ptr())))
+        bi = self._buf("fuse_bi", max(nnb * n_kp + n_tp, 1), torch.int32)
+        bd = self._buf("fuse_bd", max(nnb * n_kp + n_tp, 1), torch.int32)
         nt = nnb * kf.n
-        mark("create_new_map_points")
-        # ---- SearchInNeighbors: Fuse(target, keyframe's points) per target, Fuse(keyframe, targets' points)
-        if nnb:
-            check("orbmi_fuse_search_batch", L.orbmi_fuse_search_batch(
-                m, nnb, kf2, _vp(d_kp), None, int(n_kp), 3.0, _vp(bi.data_ptr()), _vp(bd.data_ptr()), None))
         o = nnb * n_kp
-        check("orbmi_fuse_search", L.orbmi_fuse_search(
-            m, C.addressof(kf.view), _vp(d_tp), None, int(n_tp), 3.0, _vp(bi.data_ptr() + 4 * o),
-            _vp(bd.data_ptr() + 4 * o), None))
-        mark("fuse")
-        # ComputeDistinctiveDescriptors + UpdateNormalAndDepth of the keyframe's points after fusion
-        check("orbmi_compute_distinctive_descriptors", L.orbmi_compute_distinctive_descriptors(
-            m, _vp(d_obs), _vp(d_off), int(npts), _vp(best.data_ptr()), _vp(dsc.data_ptr())))
-        mark("distinctive")
-        # (the next queued keyframe's ComputeBoW: _on_ba_enqueued, from inside this call)
-        # ---- LocalBundleAdjustment (same stream, so it runs behind the searches above)
-        self.last = self.ba.run(job.problem)
+        if native:
+            nw, nn = self._run_job_native(job, b, counts_h, best, dsc, tri, tri_ok, x3d, bi, bd,
+                                          stage_ev if je is not None else None)
+            if je is not None:
+                marks = list(zip(("bow_distinctive", "create_new_map_points", "fuse", "distinctive"), stage_ev))
+        else:
+            nw, nn = self._run_job_calls(job, b, counts_h, best, dsc, distinctive, tri, tri_ok, x3d, bi, bd, mark)
         ms = self._ms
         if je is not None:  # LocalBA returned: its work is complete
             e1 = torch.cuda.Event(enable_timing=True)
@@ -688,6 +699,80 @@ class LocalMapper:
                                                            b["off"][:nn + 1].cpu().numpy(),
                                                            b["feat"][:kf.n].cpu().numpy()))
         return out
+
+    def _run_job_native(self, job, b, counts_h, best, dsc, tri, tri_ok, x3d, bi, bd, stage_ev):
+        """The chain as one call (orbmi_local_mapping_job): the job's struct completed with this
+        mapper's BowVector / FeatureVector set, output buffers and the LocalBA result; the GIL is
+        released for the whole job.  -> (BowVector size, FeatureVector node count)."""
+        from .types import LMJobResult
+        c = job.c_job
+        # without the transform ahead the call issues ComputeBoW and the size copy itself
+        c.voc = None if self._prebow else self.voc._h
+        c.bow_word, c.bow_value = b["word"].data_ptr(), b["value"].data_ptr()
+        c.fv_node, c.fv_off, c.fv_feat = b["node"].data_ptr(), b["off"].data_ptr(), b["feat"].data_ptr()
+        c.bow_counts = b["counts"].data_ptr()
+        c.counts_host, c.counts_event = counts_h._h, counts_h._ev
+        c.best, c.desc_out = best.data_ptr(), dsc.data_ptr()
+        c.match12, c.ok, c.x3d = tri.data_ptr(), tri_ok.data_ptr(), x3d.data_ptr()
+        c.best_idx, c.best_dist = bi.data_ptr(), bd.data_ptr()
+        problem = job.problem
+        r, tcw, pos, erase = problem.result_buffers()
+        v = problem.view()
+        c.problem, c.result, c.stop = C.addressof(v), C.addressof(r), None
+        evs = None
+        if stage_ev is not None:
+            evs = (C.c_void_p * 4)(*[ev.cuda_event for ev in stage_ev])
+        c.stage_events = C.addressof(evs) if evs is not None else None
+        res = LMJobResult()
+        # (the next queued keyframe's ComputeBoW: _on_ba_enqueued, from inside this call)
+        check("orbmi_local_mapping_job", lib().orbmi_local_mapping_job(self.matcher._h, self.ba._h, C.addressof(c),
+                                                                       C.addressof(res)))
+        self.last = self.ba.result(problem, r, tcw, pos, erase)
+        return res.bow_words, res.fv_nodes
+
+    def _run_job_calls(self, job, b, counts_h, best, dsc, distinctive, tri, tri_ok, x3d, bi, bd, mark):
+        """The chain call by call over the per-operator entries (ORBMI_LM_NATIVE=0)."""
+        from .types import FeatureVectorView
+        L = lib()
+        m = self.matcher._h
+        kf = job.kf
+        nnb = len(job.neighbours)
+        d_kp, n_kp = job.kf_points
+        d_tp, n_tp = job.target_points
+        d_obs, d_off, npts = job.obs
+        kf2 = job.c_kf2
+        mark("bow_distinctive")
+        # waits for the size copy only (whatever the stream mode).  With the transform ahead the
+        # copy follows the transform on the vocabulary's stream, so once the host has read the
+        # sizes the FeatureVector is complete too and the mapper's stream needs no cross-stream
+        # wait (a wait packet costs the stream ~10 us)
+        nw, nn = counts_h.read()
+        # ---- CreateNewMapPoints: every neighbour's SearchForTriangulation and the triangulation /
+        # acceptance geometry on the device, in the reference's pair order (orbmi_create_new_map_points)
+        fv1 = FeatureVectorView(nn, b["node"].data_ptr(), b["off"].data_ptr(), b["feat"].data_ptr())
+        if nnb:
+            check("orbmi_create_new_map_points", L.orbmi_create_new_map_points(
+                m, C.addressof(kf.view), C.addressof(kf.tri_dev), _vp(kf.d_cos.data_ptr()), _vp(kf.d_has_mp),
+                C.addressof(fv1), nnb, kf2, job.c_tri2, job.c_cos2, job.c_mp2, job.c_fv2, job.c_F12.ctypes.data,
+                _vp(tri.data_ptr()), _vp(tri_ok.data_ptr()), _vp(x3d.data_ptr())))
+        mark("create_new_map_points")
+        # ---- SearchInNeighbors: Fuse(target, keyframe's points) per target, Fuse(keyframe, targets' points)
+        if nnb:
+            check("orbmi_fuse_search_batch", L.orbmi_fuse_search_batch(
+                m, nnb, kf2, _vp(d_kp), None, int(n_kp), 3.0, _vp(bi.data_ptr()), _vp(bd.data_ptr()), None))
+        o = nnb * n_kp
+        check("orbmi_fuse_search", L.orbmi_fuse_search(
+            m, C.addressof(kf.view), _vp(d_tp), None, int(n_tp), 3.0, _vp(bi.data_ptr() + 4 * o),
+            _vp(bd.data_ptr() + 4 * o), None))
+        mark("fuse")
+        # ComputeDistinctiveDescriptors + UpdateNormalAndDepth of the keyframe's points after fusion
+        check("orbmi_compute_distinctive_descriptors", L.orbmi_compute_distinctive_descriptors(
+            m, _vp(d_obs), _vp(d_off), int(npts), _vp(best.data_ptr()), _vp(dsc.data_ptr())))
+        mark("distinctive")
+        # (the next queued keyframe's ComputeBoW: _on_ba_enqueued, from inside this call)
+        # ---- LocalBundleAdjustment (same stream, so it runs behind the searches above)
+        self.last = self.ba.run(job.problem)
+        return nw, nn
 
     def last_job_outputs(self):
         """What the last finished LocalMappingJob's searches found, read back (call after wait()):

@@ -166,6 +166,27 @@ class BAResultView(C.Structure):
                 ("chi2", C.c_double * 2), ("aborted", C.c_int), ("stop_check", C.c_int), ("checks", C.c_int)]
 
 
+class LMJob(C.Structure):
+    """orbmi_lm_job: one LocalMapping::Run iteration for orbmi_local_mapping_job (include/orbmi.h)."""
+    _fields_ = [("voc", C.c_void_p), ("bow_desc", C.c_void_p), ("bow_n", C.c_int), ("bow_word", C.c_void_p),
+                ("bow_value", C.c_void_p), ("fv_node", C.c_void_p), ("fv_off", C.c_void_p), ("fv_feat", C.c_void_p),
+                ("bow_counts", C.c_void_p), ("counts_host", C.c_void_p), ("counts_event", C.c_void_p),
+                ("obs_desc", C.c_void_p), ("obs_off", C.c_void_p), ("n_points", C.c_int), ("best", C.c_void_p),
+                ("desc_out", C.c_void_p),
+                ("kf", C.c_void_p), ("tri", C.c_void_p), ("cos", C.c_void_p), ("has_mp", C.c_void_p), ("nnb", C.c_int),
+                ("kf2", C.c_void_p), ("tri2", C.c_void_p), ("cos2", C.c_void_p), ("has_mp2", C.c_void_p),
+                ("fv2", C.c_void_p), ("F12", C.c_void_p), ("match12", C.c_void_p), ("ok", C.c_void_p),
+                ("x3d", C.c_void_p),
+                ("kf_points", C.c_void_p), ("n_kf_points", C.c_int), ("target_points", C.c_void_p),
+                ("n_target_points", C.c_int), ("fuse_th", C.c_float), ("best_idx", C.c_void_p),
+                ("best_dist", C.c_void_p),
+                ("problem", C.c_void_p), ("result", C.c_void_p), ("stop", C.c_void_p), ("stage_events", C.c_void_p)]
+
+
+class LMJobResult(C.Structure):
+    _fields_ = [("bow_words", C.c_int), ("fv_nodes", C.c_int), ("failed_stage", C.c_int)]
+
+
 class BAProblem:
     """Local-BA graph as the C ABI takes it; keeps arrays alive for the views."""
 
