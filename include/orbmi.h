@@ -868,6 +868,82 @@ int orbmi_slam_save_trajectory_kitti(orbmi_slam* h, const char* path);
 int orbmi_slam_save_trajectory_tum(orbmi_slam* h, const char* path);
 int orbmi_slam_save_keyframe_trajectory_tum(orbmi_slam* h, const char* path);
 
+/* ---- LoopClosing::ComputeSim3: Sim3Solver ------------------------------------------- */
+
+/* One Sim3Solver after its constructor's filtering (src/Sim3Solver.cc:62-103): the n kept
+ * correspondences.  x3d_c1 / x3d_c2 = mvX3Dc1 / mvX3Dc2 (n x 3, camera frames), max_err1 /
+ * max_err2 = mvnMaxError1 / 2 (9.210 * sigma2 truncated to an integer, as the reference's
+ * vector<size_t> stores it), k1 / k2 = fx fy cx cy of mK1 / mK2, fix_scale = mbFixScale; then the
+ * arguments of SetRansacParameters (:114-138).  The arrays may be host or device memory.
+ * triples: the minimal sets, iterations x 3 indices into the n correspondences (host memory,
+ * iterations = orbmi_sim3_iterations), or NULL to draw them as orbmi_sim3_sample_triples does
+ * from (seed, the solver's position in the batch, the iteration). */
+typedef struct orbmi_sim3_problem {
+    int32_t n;
+    const float* x3d_c1;
+    const float* x3d_c2;
+    const int32_t* max_err1;
+    const int32_t* max_err2;
+    float k1[4], k2[4];
+    int32_t fix_scale;
+    double probability;
+    int32_t min_inliers;
+    int32_t max_iterations;
+    const int32_t* triples;
+    uint64_t seed;
+} orbmi_sim3_problem;
+
+/* Every hypothesis of one solver: what iteration h of Sim3Solver::iterate (:160-213) computes
+ * before it compares with the best.  iterations (out) = mRansacMaxIts after SetRansacParameters,
+ * 0 when n < min_inliers (iterate returns bNoMore at once, :147-151).  The arrays (host or device
+ * memory, room for max_iterations hypotheses) receive per hypothesis h: rows 0-2 of mT12i and
+ * mT21i (row-major 3x4), ms12i, mnInliersi, and mvbInliersi as a bitmask of (n + 63) / 64 64-bit
+ * words (bit i & 63 of word i >> 6 = correspondence i). */
+typedef struct orbmi_sim3_hypotheses {
+    int32_t iterations;
+    float* T12;
+    float* T21;
+    float* s;
+    int32_t* count;
+    uint64_t* mask;
+} orbmi_sim3_hypotheses;
+
+/* ComputeSim3 (:239-351) and CheckInliers (:354-378) for every iteration of `nsolvers` solvers in
+ * one launch on the matcher handle's stream (the candidate loop of LoopClosing::ComputeSim3,
+ * src/LoopClosing.cc:349-398, runs 5 iterations per candidate per round, sequentially).  The
+ * caller replays iterate's best / return rule over the arrays (orbmi::Sim3Solver in orbmi.hpp).
+ * ORBMI_E_ARG before anything is launched: n < 3 (with n >= min_inliers), an index of `triples`
+ * outside [0, n), a NULL array.  Host outputs are complete on return; with every output in
+ * device memory the call is asynchronous. */
+int orbmi_sim3_ransac_batch(orbmi_matcher* m, int nsolvers, const orbmi_sim3_problem* problems,
+                            orbmi_sim3_hypotheses* results);
+/* SetRansacParameters' iteration count (:125-135); 0 when n < min_inliers.  Host only. */
+int orbmi_sim3_iterations(int n, int min_inliers, double probability, int max_iterations, int* out);
+/* The minimal sets of :167-185 (draw, swap with the back, pop; three times) from the library's
+ * counter-based generator (csrc/sim3_horn.h): out = iterations x 3.  Host only. */
+int orbmi_sim3_sample_triples(uint64_t seed, int solver, int n, int iterations, int32_t* out);
+/* mvnMaxError's entry for one level (:87-88): (size_t)(9.210 * sigma2).  Host only. */
+int orbmi_sim3_max_error(float sigma2, int32_t* out);
+
+/* ---- LoopClosing::ComputeSim3: ORBmatcher::SearchBySim3 ------------------------------ */
+
+/* ORBmatcher::SearchBySim3(pKF1, pKF2, vpMatches12, s12, R12, t12, th) (src/ORBmatcher.cc:
+ * 1285-1525): KF1's map points searched in KF2 and KF2's in KF1 under the Sim3 (s12, R12, t12:
+ * camera 2 -> camera 1; R12 = 9 floats row-major, t12 = 3 floats, host memory), then the mutual
+ * agreement check.  mps1 / mps2: one orbmi_mappoint per keypoint slot of KF1 / KF2
+ * (GetMapPointMatches), has_mp1 / has_mp2[i] = GetMapPoint(i) != NULL.  match12 (KF1.n entries,
+ * read and written) on entry: -1 = vpMatches12[i] NULL, >= 0 = vpMatches12[i]->
+ * GetIndexInKeyFrame(pKF2), -2 = matched to a point without an index in KF2; on exit the new
+ * matches are added (match12[i1] = the KF2 slot whose point vpMatches12[i1] becomes).  *nfound =
+ * the return value.  vn_match1 (KF1.n) / vn_match2 (KF2.n): vnMatch1 / vnMatch2 before the
+ * agreement check, optional (NULL).  Both directions project with KF1's fx, fy, cx, cy, as the
+ * reference does (:1289-1292 used at :1363 and :1447); the keyframes' poses are host memory.
+ * ORBMI_E_UNSUPPORTED above 16384 keypoints, as orbmi_fuse_search. */
+int orbmi_search_by_sim3(orbmi_matcher* m, const orbmi_frame_view* KF1, const orbmi_mappoint* mps1,
+                         const uint8_t* has_mp1, const orbmi_frame_view* KF2, const orbmi_mappoint* mps2,
+                         const uint8_t* has_mp2, float s12, const float* R12, const float* t12, float th,
+                         int32_t* match12, int* nfound, int32_t* vn_match1, int32_t* vn_match2);
+
 /* ---- per-stage timing (HIP events on the handle's stream) ---------------------------- */
 
 /* Kernel stages of one handle; each is a single kernel launch (resize: one per level). */

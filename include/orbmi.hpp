@@ -232,6 +232,24 @@ public:
         return n;
     }
 
+    // SearchBySim3(KeyFrame*, KeyFrame*, vector<MapPoint*>& vpMatches12, s12, R12, t12, th)
+    // (src/ORBmatcher.cc:1285-1525): mps / hasMapPoint one record and flag per keypoint slot,
+    // match12 as orbmi.h codes vpMatches12 (-1 none, >= 0 the KF2 slot, -2 a point without an index
+    // in KF2), updated with the new matches.  Returns nFound.
+    int SearchBySim3(const orbmi_frame_view& KF1, const std::vector<orbmi_mappoint>& mps1,
+                     const std::vector<uint8_t>& hasMapPoint1, const orbmi_frame_view& KF2,
+                     const std::vector<orbmi_mappoint>& mps2, const std::vector<uint8_t>& hasMapPoint2,
+                     std::vector<int32_t>& match12, float s12, const float R12[9], const float t12[3], float th) {
+        if ((int)mps1.size() != KF1.n || (int)hasMapPoint1.size() != KF1.n || (int)match12.size() != KF1.n ||
+            (int)mps2.size() != KF2.n || (int)hasMapPoint2.size() != KF2.n)
+            throw Error(ORBMI_E_ARG, "ORBmatcher::SearchBySim3");
+        int n = 0;
+        check(orbmi_search_by_sim3(h_, &KF1, mps1.data(), hasMapPoint1.data(), &KF2, mps2.data(), hasMapPoint2.data(), s12,
+                                   R12, t12, th, match12.data(), &n, nullptr, nullptr),
+              "orbmi_search_by_sim3");
+        return n;
+    }
+
     // MapPoint::ComputeDistinctiveDescriptors (src/MapPoint.cc:247-316) for a batch of points
     void ComputeDistinctiveDescriptors(const std::vector<uint8_t>& obsDesc, const std::vector<int32_t>& obsOff,
                                        std::vector<int32_t>& best, std::vector<uint8_t>& descOut) {
@@ -330,6 +348,126 @@ public:
 
 private:
     orbmi_ba* h_ = nullptr;
+};
+
+// ORB_SLAM2::Sim3Solver (include/Sim3Solver.h:37-130, src/Sim3Solver.cc) over the flat arrays the
+// reference's constructor builds (:62-103: mvX3Dc1 / mvX3Dc2, mvnMaxError1 / 2, mvnIndices1, mN1,
+// mK1 / mK2).  The device computes every hypothesis (orbmi_sim3_ransac_batch); iterate replays the
+// reference's best / return rule over them.  Several solvers share one launch through SolveBatch
+// (the candidate loop of LoopClosing::ComputeSim3, src/LoopClosing.cc:349-398); a solver that was
+// not part of a batch solves itself on its first iterate.  The arrays are copied.
+class Sim3Solver {
+public:
+    Sim3Solver(std::vector<float> x3Dc1, std::vector<float> x3Dc2, std::vector<int32_t> maxError1,
+               std::vector<int32_t> maxError2, std::vector<int32_t> indices1, int N1, const float K1[4],
+               const float K2[4], bool bFixScale, uint64_t seed = 0)
+        : x1_(std::move(x3Dc1)), x2_(std::move(x3Dc2)), e1_(std::move(maxError1)), e2_(std::move(maxError2)),
+          idx1_(std::move(indices1)), mN1(N1), N((int)e1_.size()), mbFixScale(bFixScale), seed_(seed) {
+        for (int k = 0; k < 4; k++) { k1_[k] = K1[k]; k2_[k] = K2[k]; }
+        SetRansacParameters();  // :111
+    }
+
+    // :114-138
+    void SetRansacParameters(double probability = 0.99, int minInliers = 6, int maxIterations = 300) {
+        mRansacProb = probability;
+        mRansacMinInliers = minInliers;
+        maxIterations_ = maxIterations;
+        check(orbmi_sim3_iterations(N, minInliers, probability, maxIterations, &mRansacMaxIts), "orbmi_sim3_iterations");
+        mnIterations = 0;
+        mnBestInliers = 0;
+        best_ = -1;
+        solved_ = false;
+    }
+
+    // Minimal sets to use instead of the library's sampler: mRansacMaxIts x 3 indices
+    void SetTriples(std::vector<int32_t> triples) { triples_ = std::move(triples); solved_ = false; }
+
+    // Every hypothesis of the solvers in one launch on the matcher's stream
+    static void SolveBatch(ORBmatcher& matcher, const std::vector<Sim3Solver*>& solvers) {
+        std::vector<orbmi_sim3_problem> P(solvers.size());
+        std::vector<orbmi_sim3_hypotheses> R(solvers.size());
+        for (size_t k = 0; k < solvers.size(); k++) {
+            Sim3Solver& s = *solvers[k];
+            const size_t H = (size_t)(s.mRansacMaxIts > 0 ? s.mRansacMaxIts : 1), words = ((size_t)s.N + 63) / 64;
+            s.T12_.assign(12 * H, 0.0f); s.T21_.assign(12 * H, 0.0f); s.s_.assign(H, 0.0f);
+            s.count_.assign(H, 0); s.mask_.assign(H * (words ? words : 1), 0);
+            if (!s.triples_.empty() && s.triples_.size() < 3 * H) throw Error(ORBMI_E_ARG, "Sim3Solver::SetTriples");
+            P[k] = orbmi_sim3_problem{s.N, s.x1_.data(), s.x2_.data(), s.e1_.data(), s.e2_.data(),
+                                      {s.k1_[0], s.k1_[1], s.k1_[2], s.k1_[3]}, {s.k2_[0], s.k2_[1], s.k2_[2], s.k2_[3]},
+                                      s.mbFixScale, s.mRansacProb, s.mRansacMinInliers, s.maxIterations_,
+                                      s.triples_.empty() ? nullptr : s.triples_.data(), s.seed_};
+            R[k] = orbmi_sim3_hypotheses{0, s.T12_.data(), s.T21_.data(), s.s_.data(), s.count_.data(), s.mask_.data()};
+        }
+        check(orbmi_sim3_ransac_batch(matcher.handle(), (int)solvers.size(), P.data(), R.data()), "orbmi_sim3_ransac_batch");
+        for (Sim3Solver* s : solvers) s->solved_ = true;
+    }
+
+    // cv::Mat iterate(int nIterations, bool& bNoMore, vector<bool>& vbInliers, int& nInliers) (:140-220):
+    // true and T12 (16 floats, row-major) when the reference returns a non-empty matrix
+    bool iterate(ORBmatcher& matcher, int nIterations, bool& bNoMore, std::vector<bool>& vbInliers, int& nInliers,
+                 float T12[16]) {
+        bNoMore = false;
+        vbInliers.assign(mN1, false);
+        nInliers = 0;
+        if (N < mRansacMinInliers) {
+            bNoMore = true;
+            return false;
+        }
+        if (!solved_) SolveBatch(matcher, {this});
+        const size_t words = ((size_t)N + 63) / 64;
+        int nCurrentIterations = 0;
+        while (mnIterations < mRansacMaxIts && nCurrentIterations < nIterations) {
+            nCurrentIterations++;
+            const int h = mnIterations++;
+            if (count_[h] >= mnBestInliers) {
+                mnBestInliers = count_[h];
+                best_ = h;
+                if (count_[h] > mRansacMinInliers) {
+                    nInliers = count_[h];
+                    for (int i = 0; i < N; i++)
+                        if (mask_[h * words + (i >> 6)] >> (i & 63) & 1) vbInliers[idx1_[i]] = true;
+                    for (int j = 0; j < 12; j++) T12[j] = T12_[12 * (size_t)h + j];
+                    T12[12] = T12[13] = T12[14] = 0.0f;
+                    T12[15] = 1.0f;
+                    return true;
+                }
+            }
+        }
+        if (mnIterations >= mRansacMaxIts) bNoMore = true;
+        return false;
+    }
+
+    // :222-226
+    bool find(ORBmatcher& matcher, std::vector<bool>& vbInliers12, int& nInliers, float T12[16]) {
+        bool bFlag;
+        return iterate(matcher, mRansacMaxIts, bFlag, vbInliers12, nInliers, T12);
+    }
+
+    // mBestScale, mBestTranslation, mBestRotation (= sR12 / s, one float division per entry) of
+    // the best hypothesis so far; valid after an iterate that ran at least one iteration
+    float GetEstimatedScale() const { return s_[best_]; }
+    void GetEstimatedTranslation(float t[3]) const {
+        for (int r = 0; r < 3; r++) t[r] = T12_[12 * (size_t)best_ + 4 * r + 3];
+    }
+    void GetEstimatedRotation(float R[9]) const {
+        for (int r = 0; r < 3; r++)
+            for (int c = 0; c < 3; c++) R[3 * r + c] = T12_[12 * (size_t)best_ + 4 * r + c] / s_[best_];
+    }
+    int GetIterations() const { return mRansacMaxIts; }
+
+private:
+    std::vector<float> x1_, x2_;
+    std::vector<int32_t> e1_, e2_, idx1_, triples_;
+    float k1_[4], k2_[4];
+    int mN1, N;
+    bool mbFixScale;
+    uint64_t seed_;
+    double mRansacProb = 0.99;
+    int mRansacMinInliers = 6, mRansacMaxIts = 0, maxIterations_ = 300, mnIterations = 0, mnBestInliers = 0, best_ = -1;
+    bool solved_ = false;
+    std::vector<float> T12_, T21_, s_;
+    std::vector<int32_t> count_;
+    std::vector<uint64_t> mask_;
 };
 
 // ORB_SLAM2::System for the RGB-D sensor (include/System.h:58-83, src/System.cc:161-210) over the

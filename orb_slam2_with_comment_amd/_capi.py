@@ -126,6 +126,11 @@ _PROTOS = {
     "orbmi_cvt_gray": (_i, [_i, _vp, _sz, _i, _i, _i, _i, _vp, _sz]),
     "orbmi_slam_create_rgbd": (_i, [_vp, _vp, _i, _vp, C.POINTER(_vp)]),
     "orbmi_slam_track_rgbd": (_i, [_vp, _vp, _i, _sz, _vp, _i, _sz, _i, _i, C.c_double, _vp, C.POINTER(_i)]),
+    "orbmi_sim3_ransac_batch": (_i, [_vp, _i, _vp, _vp]),
+    "orbmi_search_by_sim3": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _vp, _vp, _f, _vp, C.POINTER(_i), _vp, _vp]),
+    "orbmi_sim3_iterations": (_i, [_i, _i, C.c_double, _i, C.POINTER(_i)]),
+    "orbmi_sim3_sample_triples": (_i, [C.c_uint64, _i, _i, _i, _vp]),
+    "orbmi_sim3_max_error": (_i, [_f, C.POINTER(C.c_int32)]),
     "orbmi_slam_create": (_i, [_vp, _i, _vp, C.POINTER(_vp)]),
     "orbmi_slam_destroy": (None, [_vp]),
     "orbmi_slam_wait_local_mapping": (_i, [_vp]),

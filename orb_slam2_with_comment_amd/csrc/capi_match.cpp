@@ -5,6 +5,8 @@
 #include <new>
 
 #include "matcher.h"
+#include "sim3.h"
+#include "sim3_horn.h"
 #include "tri_geom.h"
 
 using orbmi::DevFrame;
@@ -1064,6 +1066,129 @@ int orbmi_local_mapping_job(orbmi_matcher* h, orbmi_ba* ba, const orbmi_lm_job* 
     // ---- LocalBundleAdjustment (in stream order behind the searches when ba runs on this stream)
     if ((rc = orbmi_local_bundle_adjustment(ba, J->problem, J->result, J->stop))) return fail(5, rc);
     return ORBMI_OK;
+}
+
+int orbmi_sim3_ransac_batch(orbmi_matcher* h, int nsolvers, const orbmi_sim3_problem* problems,
+                            orbmi_sim3_hypotheses* results) {
+    if (!h || nsolvers < 0 || (nsolvers > 0 && (!problems || !results))) return ORBMI_E_ARG;
+    // everything is validated before anything is staged or launched
+    std::vector<int> its((size_t)nsolvers);
+    int max_its = 0;
+    for (int k = 0; k < nsolvers; k++) {
+        const orbmi_sim3_problem& P = problems[k];
+        if (P.n < 0 || P.min_inliers < 0 || P.max_iterations < 0) return ORBMI_E_ARG;
+        its[k] = orbmi::sim3_iterations(P.n, P.min_inliers, P.probability, P.max_iterations);
+        if (its[k] == 0) continue;
+        const orbmi_sim3_hypotheses& R = results[k];
+        if (P.n < 3 || !P.x3d_c1 || !P.x3d_c2 || !P.max_err1 || !P.max_err2 || !R.T12 || !R.T21 || !R.s || !R.count ||
+            !R.mask)
+            return ORBMI_E_ARG;
+        if (P.triples) {
+            if (on_device(P.triples)) return ORBMI_E_ARG;
+            for (int j = 0; j < 3 * its[k]; j++)
+                if (P.triples[j] < 0 || P.triples[j] >= P.n) return ORBMI_E_ARG;
+        }
+        max_its = std::max(max_its, its[k]);
+    }
+    for (int k = 0; k < nsolvers; k++) results[k].iterations = its[k];
+    if (max_its == 0) return ORBMI_OK;
+    Matcher& m = h->m;
+    ORBMI_HIP(hipSetDevice(m.device));
+    m.arena_reset();
+    int rc = 0;
+    std::vector<OutBuf> outs;
+    std::vector<orbmi::Sim3Dev> T((size_t)nsolvers);
+    std::vector<int32_t> tri, avail;
+    for (int k = 0; k < nsolvers; k++) {
+        const orbmi_sim3_problem& P = problems[k];
+        orbmi::Sim3Dev& D = T[k];
+        memset(&D, 0, sizeof(D));
+        D.n = P.n;
+        D.iterations = its[k];
+        if (its[k] == 0) continue;
+        const size_t n = (size_t)P.n, H = (size_t)its[k], words = (n + 63) / 64;
+        D.fix_scale = P.fix_scale;
+        D.x1 = dev_in(m, P.x3d_c1, 3 * n, &rc);
+        D.x2 = dev_in(m, P.x3d_c2, 3 * n, &rc);
+        D.e1 = dev_in(m, P.max_err1, n, &rc);
+        D.e2 = dev_in(m, P.max_err2, n, &rc);
+        memcpy(D.k1, P.k1, sizeof(D.k1));
+        memcpy(D.k2, P.k2, sizeof(D.k2));
+        if (P.triples) {
+            D.triples = dev_in(m, P.triples, 3 * H, &rc);
+        } else {
+            tri.resize(3 * H);
+            avail.resize(n);
+            for (int it = 0; it < its[k]; it++)
+                orbmi::sim3_sample_triple(P.seed, k, it, P.n, avail.data(), tri.data() + 3 * (size_t)it);
+            D.triples = dev_in(m, (const int32_t*)tri.data(), 3 * H, &rc);  // copied into the arena's mirror at once
+        }
+        if (rc) return rc;
+        const orbmi_sim3_hypotheses& R = results[k];
+        D.T12 = dev_out(m, R.T12, 12 * H, outs);
+        D.T21 = dev_out(m, R.T21, 12 * H, outs);
+        D.s = dev_out(m, R.s, H, outs);
+        D.count = dev_out(m, R.count, H, outs);
+        D.mask = dev_out(m, R.mask, H * words, outs);
+        if (!D.T12 || !D.T21 || !D.s || !D.count || !D.mask) return ORBMI_E_HIP;
+    }
+    const orbmi::Sim3Dev* d_T = dev_in(m, (const orbmi::Sim3Dev*)T.data(), (size_t)nsolvers, &rc);
+    if (rc) return rc;
+    if ((rc = orbmi::launch_sim3_ransac(m, nsolvers, d_T, max_its))) return rc;
+    return finish(m, outs, nullptr, nullptr);
+}
+
+int orbmi_search_by_sim3(orbmi_matcher* h, const orbmi_frame_view* kf1, const orbmi_mappoint* mps1, const uint8_t* has_mp1,
+                         const orbmi_frame_view* kf2, const orbmi_mappoint* mps2, const uint8_t* has_mp2, float s12,
+                         const float* R12, const float* t12, float th, int32_t* match12, int* nfound, int32_t* vn_match1,
+                         int32_t* vn_match2) {
+    if (!h || !kf1 || !kf2 || !R12 || !t12 || kf1->n < 0 || kf2->n < 0 || (kf1->n > 0 && (!mps1 || !has_mp1 || !match12)) ||
+        (kf2->n > 0 && (!mps2 || !has_mp2)) || on_device(R12) || on_device(t12))
+        return ORBMI_E_ARG;
+    if (nfound) *nfound = 0;
+    Matcher& m = h->m;
+    ORBMI_HIP(hipSetDevice(m.device));
+    m.arena_reset();
+    int rc = 0;
+    orbmi::Sim3Side S[2];
+    memset(S, 0, sizeof(S));
+    DevFrame K1, K2;
+    if ((rc = make_frame(m, kf1, &K1, true)) || (rc = make_frame(m, kf2, &K2, true))) return rc;
+    if (K1.tcw_dev || K2.tcw_dev) return ORBMI_E_ARG;  // the poses travel by value
+    const size_t n1 = (size_t)kf1->n, n2 = (size_t)kf2->n;
+    S[0].F = K2; S[0].n_src = kf1->n;
+    S[1].F = K1; S[1].n_src = kf2->n;
+    S[0].mps = dev_in(m, mps1, n1, &rc); S[0].has = dev_in(m, has_mp1, n1, &rc);
+    S[1].mps = dev_in(m, mps2, n2, &rc); S[1].has = dev_in(m, has_mp2, n2, &rc);
+    if (rc) return rc;
+    memcpy(S[0].Tcw, K1.tcw, sizeof(S[0].Tcw));
+    memcpy(S[1].Tcw, K2.tcw, sizeof(S[1].Tcw));
+    // sR12 = s12 * R12, sR21 = (1.0 / s12) * R12^T, t21 = -sR21 * t12 (:1304-1308): the scalar a
+    // double, the matrix float, one rounding to float per entry; the products float, left to right
+    const double inv = 1.0 / (double)s12;
+    float sR21[9];
+    for (int r = 0; r < 3; r++)
+        for (int c = 0; c < 3; c++) {
+            S[1].S[4 * r + c] = (float)((double)s12 * (double)R12[3 * r + c]);
+            sR21[3 * r + c] = (float)(inv * (double)R12[3 * c + r]);
+            S[0].S[4 * r + c] = sR21[3 * r + c];
+        }
+    for (int r = 0; r < 3; r++) {
+        S[1].S[4 * r + 3] = t12[r];
+        S[0].S[4 * r + 3] = -((sR21[3 * r] * t12[0] + sR21[3 * r + 1] * t12[1]) + sR21[3 * r + 2] * t12[2]);
+    }
+    for (int k = 0; k < 2; k++) { S[k].fx = kf1->fx; S[k].fy = kf1->fy; S[k].cx = kf1->cx; S[k].cy = kf1->cy; }
+    std::vector<OutBuf> outs;
+    int* d_m12 = dev_out(m, match12, n1, outs);
+    if (!on_device(match12) && n1) ORBMI_HIP(m.h2d(d_m12, match12, n1 * sizeof(int32_t)));
+    S[0].vn = vn_match1 ? dev_out(m, vn_match1, n1, outs) : (int*)m.stage(std::max(n1, (size_t)1) * sizeof(int));
+    S[1].vn = vn_match2 ? dev_out(m, vn_match2, n2, outs) : (int*)m.stage(std::max(n2, (size_t)1) * sizeof(int));
+    uint8_t* d_already2 = (uint8_t*)m.stage(std::max(n2, (size_t)1));
+    orbmi::Sim3Side* d_S = (orbmi::Sim3Side*)m.stage(sizeof(S));
+    if (!d_m12 || !S[0].vn || !S[1].vn || !d_already2 || !d_S) return ORBMI_E_HIP;
+    if ((rc = scalars(m))) return rc;
+    if ((rc = orbmi::launch_search_by_sim3(m, S, d_S, d_m12, d_already2, th, m.d_scalars))) return rc;
+    return finish(m, outs, m.d_scalars, nfound);
 }
 
 int orbmi_debug_greedy_stats(unsigned long long* out, int reset) {

@@ -71,6 +71,22 @@ struct FuseKF {
     int* ncand;             // one int
 };
 
+// One direction of SearchBySim3 (grid row): the source keyframe's points searched in the target
+// keyframe F
+struct Sim3Side {
+    DevFrame F;                  // target keyframe (keys, descriptors, bounds, scale table)
+    int* cs;                     // its grid: cell_start (kGridCells + 1), cell_list, kp_cell
+    int* cl;
+    int* kc;
+    const orbmi_mappoint* mps;   // the source keyframe's map points, one per keypoint slot
+    const uint8_t* has;          // GetMapPoint(i) != NULL
+    int n_src;
+    float Tcw[12];               // rows 0-2 of the source keyframe's pose
+    float S[12];                 // [sR | t]: source camera -> target camera
+    float fx, fy, cx, cy;        // KF1's in both directions (src/ORBmatcher.cc:1289-1292)
+    int* vn;                     // vnMatch of this direction (n_src)
+};
+
 struct Matcher {
     static constexpr int kCandCap = 96;  // candidates kept per query; overflow re-enumerates
     int device = 0;
@@ -185,6 +201,8 @@ int fuse_multi_prepare(Matcher& m, int nkf, FuseKF* kfs_host, int n, int* best_i
 // kfs_host == nullptr: the table is already prepared (fuse_multi_prepare -> ncap) and uploaded
 int launch_fuse_multi(Matcher& m, int nkf, FuseKF* kfs_host, FuseKF* kfs_dev, const orbmi_mappoint* mps, int n,
                       float th, int* best_idx, int* best_dist, int* ncand, int ncap = 0);
+int launch_search_by_sim3(Matcher& m, Sim3Side* sides_host, Sim3Side* sides_dev, int* match12, uint8_t* already2, float th,
+                          int* nfound);
 int launch_patch_desc(Matcher& m, orbmi_mappoint* mps, const int* desc_from, const uint8_t* desc, int n);
 int greedy_stats(unsigned long long out[5], int reset);
 int greedy_cycles(unsigned long long out[7], int reset);

@@ -1911,6 +1911,115 @@ int launch_fuse_multi(Matcher& m, int nkf, FuseKF* kfs_host, FuseKF* kfs_dev, co
     return hipGetLastError() == hipSuccess ? ORBMI_OK : ORBMI_E_HIP;
 }
 
+// -------------------------------------------------------------------------- SearchBySim3
+// ORBmatcher::SearchBySim3 (src/ORBmatcher.cc:1285-1525): both projection-guided searches in one
+// launch (grid row 0: KF1's points into KF2, row 1: KF2's points into KF1), built from the parts of
+// the Fuse search, then the agreement pass.  Per point, in the reference's order: no point /
+// already matched / bad; p3Dc = Rcw Xw + tcw and the Sim3 transform into the target camera; z < 0;
+// KeyFrame::IsInImage of the target; dist3D inside [0.8 min, 1.2 max]; PredictScale against the
+// target; radius = th * scale[level]; GetFeaturesInArea without level limits; the octave window
+// [level - 1, level]; the best distance, <= TH_HIGH, ties to the first keypoint of the grid order.
+// Both rows project with KF1's intrinsics, as the reference does (:1289-1292 used at :1363 and :1447).
+__global__ __launch_bounds__(1024) void k_sim3_grids(const Sim3Side* __restrict__ sides, const int* __restrict__ match12,
+                                                     int n1, uint8_t* __restrict__ already2, int n2) {
+    const Sim3Side& S = sides[blockIdx.x];
+    // vbAlreadyMatched2 (:1321-1331; zeroed before this launch): every writer stores 1
+    if (blockIdx.x == 0)
+        for (int i = threadIdx.x; i < n1; i += blockDim.x) {
+            const int idx2 = match12[i];
+            if (idx2 >= 0 && idx2 < n2) already2[idx2] = 1;
+        }
+    grid_build_block(S.F, S.cs, S.cl, S.kc);
+}
+
+__global__ __launch_bounds__(256) void k_sim3_search(const Sim3Side* __restrict__ sides, const int* __restrict__ match12,
+                                                     const uint8_t* __restrict__ already2, float th) {
+    const Sim3Side& S = sides[blockIdx.y];
+    const DevFrame& F = S.F;
+    const int t = blockIdx.x * blockDim.x + threadIdx.x, i = t / kFuseLanes, glane = t % kFuseLanes;
+    if (S.n_src <= 0) return;        // the whole grid row
+    const bool valid = i < S.n_src;  // the other lanes only take part in the group minimum
+    const orbmi_mappoint mp = S.mps[valid ? i : 0];
+    bool ok = valid && S.has[i] && !(blockIdx.y == 0 ? match12[i] != -1 : already2[i] != 0) && !(mp.flags & ORBMI_MP_BAD);
+    float Pc[3] = {0, 0, 0};
+    if (ok) {
+        float Ps[3];
+        transform(S.Tcw, mp.pos, Ps);
+        transform(S.S, Ps, Pc);
+        ok = !(Pc[2] < 0.0f);
+    }
+    float u = 0, v = 0, dist3D = 0;
+    if (ok) {
+        const float invz = 1.0f / Pc[2];
+        const float x = Pc[0] * invz, y = Pc[1] * invz;
+        u = S.fx * x + S.cx;
+        v = S.fy * y + S.cy;
+        ok = u >= F.min_x && u < F.max_x && v >= F.min_y && v < F.max_y;  // KeyFrame::IsInImage
+    }
+    if (ok) {
+        const float maxDistance = 1.2f * mp.max_distance, minDistance = 0.8f * mp.min_distance;
+        dist3D = (float)sqrt(((double)Pc[0] * Pc[0] + (double)Pc[1] * Pc[1]) + (double)Pc[2] * Pc[2]);  // cv::norm
+        ok = !(dist3D < minDistance || dist3D > maxDistance);
+    }
+    unsigned long long best = ~0ull;
+    if (ok) {
+        const float ratio = mp.max_distance / dist3D;  // MapPoint::PredictScale(dist, KeyFrame*)
+        int nPredictedLevel = (int)ceilf((float)log((double)ratio) / F.log_scale_factor);
+        if (nPredictedLevel < 0) nPredictedLevel = 0;
+        else if (nPredictedLevel >= F.nlevels) nPredictedLevel = F.nlevels - 1;
+        const float radius = th * F.scale[nPredictedLevel];
+        for_features_in_area<kFuseLanes>(F, S.cs, S.cl, u, v, radius, -1, -1, glane, [&](int idx, int cell) {
+            const int kpLevel = F.keys[idx].octave;
+            if (kpLevel < nPredictedLevel - 1 || kpLevel > nPredictedLevel) return;
+            const unsigned long long e = cand_entry(popc_desc(mp.desc, F.desc + 32 * (long long)idx), cell, idx);
+            best = e < best ? e : best;
+        });
+    }
+    best = group_min_u64<kFuseLanes>(best);
+    if (!valid || glane != 0) return;
+    S.vn[i] = (best != ~0ull && (int)(best >> 40) <= TH_HIGH) ? (int)(best & 0xFFFFF) : -1;
+}
+
+// the agreement pass (:1506-1522): match12[i1] = idx2 where vnMatch2[vnMatch1[i1]] == i1
+__global__ __launch_bounds__(256) void k_sim3_agree(const int* __restrict__ vn1, const int* __restrict__ vn2, int n1,
+                                                    int* __restrict__ match12, int* __restrict__ nfound) {
+    const int i1 = blockIdx.x * blockDim.x + threadIdx.x;
+    bool found = false;
+    if (i1 < n1) {
+        const int idx2 = vn1[i1];
+        found = idx2 >= 0 && vn2[idx2] == i1;
+        if (found) match12[i1] = idx2;
+    }
+    const unsigned long long m = __ballot(found);  // one atomic per wave; an integer sum has no order
+    if (found && (threadIdx.x & 63) == __ffsll((long long)m) - 1) atomicAdd(nfound, (int)__popcll(m));
+}
+
+// sides_host: F, mps, has, n_src, Tcw, S, intrinsics and vn filled by the caller; the grids are
+// assigned here.  nfound must be zeroed by the caller (in stream order).
+int launch_search_by_sim3(Matcher& m, Sim3Side* sides_host, Sim3Side* sides_dev, int* match12, uint8_t* already2, float th,
+                          int* nfound) {
+    const int n1 = sides_host[0].n_src, n2 = sides_host[1].n_src;  // = KF1.n, KF2.n
+    if (n1 > kGreedyMaxKp || n2 > kGreedyMaxKp) return ORBMI_E_UNSUPPORTED;
+    const int ncap = std::max(std::max(n1, n2), 1);
+    int rc;
+    if ((rc = ensure_buf(&m.d_mcell_start, &m.cap_mcell_start, (size_t)(kGridCells + 1) * 2))) return rc;
+    if ((rc = ensure_buf(&m.d_mcell_list, &m.cap_mcell_list, (size_t)ncap * 2))) return rc;
+    if ((rc = ensure_buf(&m.d_mkp_cell, &m.cap_mkp_cell, (size_t)ncap * 2))) return rc;
+    for (int k = 0; k < 2; k++) {
+        sides_host[k].cs = m.d_mcell_start + (size_t)k * (kGridCells + 1);
+        sides_host[k].cl = m.d_mcell_list + (size_t)k * ncap;
+        sides_host[k].kc = m.d_mkp_cell + (size_t)k * ncap;
+    }
+    ORBMI_HIP(m.h2d(sides_dev, sides_host, sizeof(Sim3Side) * 2));
+    ORBMI_HIP(hipMemsetAsync(already2, 0, (size_t)std::max(n2, 1), m.ls()));
+    hipLaunchKernelGGL(k_sim3_grids, dim3(2), dim3(1024), 0, m.ls(), sides_dev, match12, n1, already2, n2);
+    hipLaunchKernelGGL(k_sim3_search, dim3((ncap * kFuseLanes + 255) / 256, 2), dim3(256), 0, m.ls(), sides_dev, match12,
+                       already2, th);
+    hipLaunchKernelGGL(k_sim3_agree, dim3((std::max(n1, 1) + 255) / 256), dim3(256), 0, m.ls(), sides_host[0].vn,
+                       sides_host[1].vn, n1, match12, nfound);
+    return hipGetLastError() == hipSuccess ? ORBMI_OK : ORBMI_E_HIP;
+}
+
 // records whose descriptor was just recomputed (desc_from[i] >= 0: row of `desc`) take it
 __global__ __launch_bounds__(256) void k_patch_desc(orbmi_mappoint* __restrict__ mps, const int* __restrict__ desc_from,
                                                     const uint8_t* __restrict__ desc, int n) {

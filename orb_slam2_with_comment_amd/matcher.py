@@ -114,6 +114,30 @@ class ORBmatcher:
             th, bi.ctypes.data, bd.ctypes.data, C.byref(c)))
         return bi[:n], bd[:n], c.value
 
+    def SearchBySim3(self, kf1, mps1, has_mp1, kf2, mps2, has_mp2, match12, s12, R12, t12, th=7.5):
+        """SearchBySim3(KeyFrame*, KeyFrame*, vector<MapPoint*>& vpMatches12, s12, R12, t12, th)
+        (src/ORBmatcher.cc:1285-1525): kf1 / kf2 are types.Frame, mps / has_mp one orbmi_mappoint
+        and one flag per keypoint slot, match12 as include/orbmi.h codes it (-1 none, >= 0 the KF2
+        slot, -2 a point without an index in KF2).  Returns (match12 with the new matches, nFound,
+        vnMatch1, vnMatch2)."""
+        n1, n2 = len(kf1.keys), len(kf2.keys)
+        mps1, mps2 = np.ascontiguousarray(mps1), np.ascontiguousarray(mps2)
+        h1, h2 = np.ascontiguousarray(has_mp1, np.uint8), np.ascontiguousarray(has_mp2, np.uint8)
+        if len(mps1) != n1 or len(h1) != n1 or len(mps2) != n2 or len(h2) != n2 or len(match12) != n1:
+            raise ValueError("SearchBySim3 takes one map point record, flag and match per keypoint slot")
+        m12 = np.zeros(max(n1, 1), np.int32)
+        m12[:n1] = match12
+        R = np.ascontiguousarray(R12, np.float32).reshape(3, 3)
+        t = np.ascontiguousarray(t12, np.float32).reshape(3)
+        vn1, vn2 = np.zeros(max(n1, 1), np.int32), np.zeros(max(n2, 1), np.int32)
+        n = C.c_int()
+        v1, v2 = kf1.view(), kf2.view()
+        check("orbmi_search_by_sim3", lib().orbmi_search_by_sim3(
+            self._h, C.addressof(v1), mps1.ctypes.data if n1 else None, h1.ctypes.data if n1 else None,
+            C.addressof(v2), mps2.ctypes.data if n2 else None, h2.ctypes.data if n2 else None, float(s12),
+            R.ctypes.data, t.ctypes.data, th, m12.ctypes.data, C.byref(n), vn1.ctypes.data, vn2.ctypes.data))
+        return m12[:n1], n.value, vn1[:n1], vn2[:n2]
+
     def ComputeDistinctiveDescriptors(self, obs_desc: np.ndarray, obs_off: np.ndarray, desc_out=None):
         """MapPoint::ComputeDistinctiveDescriptors (src/MapPoint.cc:247-316) for a batch of map
         points: rows obs_off[p]..obs_off[p+1] of obs_desc are point p's observation descriptors.
