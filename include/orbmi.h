@@ -944,6 +944,67 @@ int orbmi_search_by_sim3(orbmi_matcher* m, const orbmi_frame_view* KF1, const or
                          const uint8_t* has_mp2, float s12, const float* R12, const float* t12, float th,
                          int32_t* match12, int* nfound, int32_t* vn_match1, int32_t* vn_match2);
 
+/* ---- LoopClosing::ComputeSim3: ORBmatcher::SearchByProjection(KF, Scw) --------------- */
+
+/* ORBmatcher::SearchByProjection(pKF, Scw, vpPoints, vpMatched, th) (src/ORBmatcher.cc:359-479):
+ * the n points of mps (vpPoints, the loop keyframe's neighbourhood) projected into KF under the
+ * Sim3 Scw (rows 0-2 of [sRcw | t], 12 floats row-major, host memory) and matched to its
+ * keypoints.  matched (KF.n entries, host memory, read and written) codes vpMatched: -1 = NULL,
+ * >= 0 = the index in mps of the matched point, -2 = a point that is not in mps; a point already
+ * in it is skipped (spAlreadyFound), an occupied keypoint is never taken, and a keypoint taken by
+ * an earlier point of the list is skipped by later ones, as in the reference's loop.  *nmatches =
+ * the return value.  The pose of KF is not read.  ORBMI_E_ARG: an entry of matched outside
+ * [-2, n); ORBMI_E_UNSUPPORTED above 16384 keypoints, as orbmi_fuse_search. */
+int orbmi_search_by_projection_sim3(orbmi_matcher* m, const orbmi_frame_view* KF, const float* Scw,
+                                    const orbmi_mappoint* mps, int n, int32_t* matched, float th, int* nmatches);
+
+/* ---- LoopClosing::ComputeSim3: Optimizer::OptimizeSim3 ------------------------------- */
+
+/* One OptimizeSim3 problem after the reference's assembly loop (src/Optimizer.cc:1198-1281): the n
+ * kept correspondences.  x3d_c1 / x3d_c2 (n x 3): the points in their own camera frames, computed
+ * in float as R1w * P3D1w + t1w / R2w * P3D2w + t2w; obs1 / obs2 (n x 2): kpUn.pt of either
+ * keyframe; inv_sigma2_1 / 2 (n): mvInvLevelSigma2[kpUn.octave] of either side; k1 / k2 = fx fy cx
+ * cy of pKF1->mK / pKF2->mK; th2 and fix_scale the arguments; R12, t12, s12 the initial estimate
+ * as g2o::Sim3(Matrix3d, Vector3d, double) takes it.  The arrays may be host or device memory. */
+typedef struct orbmi_sim3_opt_problem {
+    int32_t n;
+    const float* x3d_c1;
+    const float* x3d_c2;
+    const float* obs1;
+    const float* obs2;
+    const float* inv_sigma2_1;
+    const float* inv_sigma2_2;
+    float k1[4], k2[4];
+    float th2;
+    int32_t fix_scale;
+    float R12[9], t12[3], s12;
+} orbmi_sim3_opt_problem;
+
+/* g2oS12 on return: q (x y z w), t, s; sR / t_f as Converter::toCvMat(g2o::Sim3) rounds them to
+ * float.  n_in = the return value (0 on the early return at nCorrespondences - nBad < 10, where
+ * the transform is the one passed in), n_bad = nBad of the first chi2 pass, iterations = the
+ * Levenberg iterations either optimize() ran.  inlier (n, host or device memory, required when
+ * n > 0): 0 where the reference nulls vpMatches1; chi2 (n x 2, optional): e12 / e21's chi2 as
+ * last tested. */
+typedef struct orbmi_sim3_opt_result {
+    double q[4], t[3], s;
+    float sR[9], t_f[3];
+    int32_t n_in, n_bad;
+    int32_t iterations[2];
+    uint8_t* inlier;
+    double* chi2;
+} orbmi_sim3_opt_result;
+
+/* Optimizer::OptimizeSim3 (src/Optimizer.cc:1145-1347) for `nproblems` independent problems in one
+ * launch on the matcher handle's stream, one workgroup each: optimize(5), the chi2 pass,
+ * optimize(5 or 10) with the Huber kernels still on, the second chi2 pass; numeric Jacobians as
+ * BaseBinaryEdge::linearizeOplus computes them.  The candidate loop of LoopClosing::ComputeSim3
+ * (src/LoopClosing.cc:399-420) takes the first problem in order with n_in >= 20.  A pair whose
+ * chi2 is NaN counts as an outlier, so a non-finite estimate returns n_in = 0.  ORBMI_E_ARG before
+ * anything is launched: a NULL table, n < 0, a NULL array of a problem with n > 0. */
+int orbmi_optimize_sim3_batch(orbmi_matcher* m, int nproblems, const orbmi_sim3_opt_problem* problems,
+                              orbmi_sim3_opt_result* results);
+
 /* ---- per-stage timing (HIP events on the handle's stream) ---------------------------- */
 
 /* Kernel stages of one handle; each is a single kernel launch (resize: one per level). */

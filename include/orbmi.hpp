@@ -250,6 +250,19 @@ public:
         return n;
     }
 
+    // SearchByProjection(KeyFrame*, cv::Mat Scw, const vector<MapPoint*>& vpPoints,
+    // vector<MapPoint*>& vpMatched, int th) (src/ORBmatcher.cc:359-479): Scw = rows 0-2 of
+    // [sRcw | t], matched one entry per keypoint slot of KF as orbmi.h codes vpMatched (-1 none,
+    // >= 0 the index in mps, -2 a point that is not in mps), updated.  Returns nmatches.
+    int SearchByProjection(const orbmi_frame_view& KF, const float Scw[12], const std::vector<orbmi_mappoint>& mps,
+                           std::vector<int32_t>& matched, int th) {
+        if ((int)matched.size() != KF.n) throw Error(ORBMI_E_ARG, "ORBmatcher::SearchByProjection(KF, Scw)");
+        int n = 0;
+        check(orbmi_search_by_projection_sim3(h_, &KF, Scw, mps.data(), (int)mps.size(), matched.data(), (float)th, &n),
+              "orbmi_search_by_projection_sim3");
+        return n;
+    }
+
     // MapPoint::ComputeDistinctiveDescriptors (src/MapPoint.cc:247-316) for a batch of points
     void ComputeDistinctiveDescriptors(const std::vector<uint8_t>& obsDesc, const std::vector<int32_t>& obsOff,
                                        std::vector<int32_t>& best, std::vector<uint8_t>& descOut) {
@@ -469,6 +482,75 @@ private:
     std::vector<int32_t> count_;
     std::vector<uint64_t> mask_;
 };
+
+// Optimizer::OptimizeSim3 (src/Optimizer.cc:1145-1347) over the arrays the reference's assembly
+// loop builds (:1198-1281): one problem per (candidate, hypothesis) pair, all of them in one launch
+// on the matcher's stream.  OptimizeSim3() takes one; OptimizeSim3Batch() several, the caller
+// taking the first in order with nIn >= 20 (src/LoopClosing.cc:399-420).
+struct Sim3OptInput {
+    std::vector<float> x3Dc1, x3Dc2;        // n x 3: R1w * P3D1w + t1w, R2w * P3D2w + t2w
+    std::vector<float> obs1, obs2;          // n x 2: kpUn.pt of either keyframe
+    std::vector<float> invSigma2_1, invSigma2_2;  // n: mvInvLevelSigma2[kpUn.octave]
+    float K1[4], K2[4];                     // fx fy cx cy
+    float th2 = 10.0f;
+    bool bFixScale = false;
+    float R12[9], t12[3], s12 = 1.0f;       // g2oS12 on entry
+};
+
+struct Sim3OptOutput {
+    double q[4], t[3], s;                   // g2oS12 on return (q = x y z w)
+    float sR[9], tf[3];                     // Converter::toCvMat(g2oS12)
+    int nIn = 0, nBad = 0, iterations[2] = {0, 0};
+    std::vector<uint8_t> inlier;            // 0 where the reference nulls vpMatches1
+};
+
+inline std::vector<Sim3OptOutput> OptimizeSim3Batch(ORBmatcher& matcher, const std::vector<Sim3OptInput>& in) {
+    std::vector<orbmi_sim3_opt_problem> P(in.size());
+    std::vector<orbmi_sim3_opt_result> R(in.size());
+    std::vector<Sim3OptOutput> out(in.size());
+    for (size_t k = 0; k < in.size(); k++) {
+        const Sim3OptInput& I = in[k];
+        const size_t n = I.invSigma2_1.size();
+        if (I.x3Dc1.size() != 3 * n || I.x3Dc2.size() != 3 * n || I.obs1.size() != 2 * n || I.obs2.size() != 2 * n ||
+            I.invSigma2_2.size() != n)
+            throw Error(ORBMI_E_ARG, "OptimizeSim3");
+        orbmi_sim3_opt_problem& p = P[k];
+        p = orbmi_sim3_opt_problem{};
+        p.n = (int32_t)n;
+        p.x3d_c1 = I.x3Dc1.data(); p.x3d_c2 = I.x3Dc2.data();
+        p.obs1 = I.obs1.data(); p.obs2 = I.obs2.data();
+        p.inv_sigma2_1 = I.invSigma2_1.data(); p.inv_sigma2_2 = I.invSigma2_2.data();
+        for (int j = 0; j < 4; j++) { p.k1[j] = I.K1[j]; p.k2[j] = I.K2[j]; }
+        p.th2 = I.th2;
+        p.fix_scale = I.bFixScale;
+        for (int j = 0; j < 9; j++) p.R12[j] = I.R12[j];
+        for (int j = 0; j < 3; j++) p.t12[j] = I.t12[j];
+        p.s12 = I.s12;
+        out[k].inlier.assign(n ? n : 1, 0);
+        R[k] = orbmi_sim3_opt_result{};
+        R[k].inlier = out[k].inlier.data();
+    }
+    check(orbmi_optimize_sim3_batch(matcher.handle(), (int)in.size(), P.data(), R.data()), "orbmi_optimize_sim3_batch");
+    for (size_t k = 0; k < in.size(); k++) {
+        Sim3OptOutput& o = out[k];
+        for (int j = 0; j < 4; j++) o.q[j] = R[k].q[j];
+        for (int j = 0; j < 3; j++) { o.t[j] = R[k].t[j]; o.tf[j] = R[k].t_f[j]; }
+        for (int j = 0; j < 9; j++) o.sR[j] = R[k].sR[j];
+        o.s = R[k].s;
+        o.nIn = R[k].n_in;
+        o.nBad = R[k].n_bad;
+        o.iterations[0] = R[k].iterations[0];
+        o.iterations[1] = R[k].iterations[1];
+        o.inlier.resize(in[k].invSigma2_1.size());
+    }
+    return out;
+}
+
+// int Optimizer::OptimizeSim3(pKF1, pKF2, vpMatches1, g2oS12, th2, bFixScale): returns nIn
+inline int OptimizeSim3(ORBmatcher& matcher, const Sim3OptInput& in, Sim3OptOutput& out) {
+    out = OptimizeSim3Batch(matcher, {in})[0];
+    return out.nIn;
+}
 
 // ORB_SLAM2::System for the RGB-D sensor (include/System.h:58-83, src/System.cc:161-210) over the
 // native loop (orbmi_slam_create_rgbd / orbmi_slam_track_rgbd).  settings: the Tracking

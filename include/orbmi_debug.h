@@ -134,6 +134,12 @@ int orbmi_slam_get_keyframe_state_log(orbmi_slam* h, orbmi_slam_kf_state* out, i
  * [28] LocalBA's graph assembly, [29] its device call, [30] its write-back. */
 int orbmi_slam_get_phase_ms(orbmi_slam* h, double* ms, int n, long* frames);
 
+/* One buildSystem pass of orbmi_optimize_sim3_batch's kernel at the problem's initial estimate
+ * (computeActiveErrors, the numeric linearizeOplus and constructQuadraticForm of every edge):
+ * H (49 doubles, row-major, before damping), b (7) and the robust chi2 (1).  Zeros when n = 0. */
+int orbmi_debug_sim3_opt_linearize(orbmi_matcher* m, const orbmi_sim3_opt_problem* problem, double* H, double* b,
+                                   double* chi2);
+
 #ifdef __cplusplus
 }
 #endif

@@ -7,6 +7,7 @@ reference interface (orb.py) used by tests and bench.py.
 """
 from .matcher import ORBmatcher  # noqa: F401
 from .orb import ORBextractor, compute_stereo_matches  # noqa: F401
-from .sim3 import Sim3Ransac, Sim3Solver, solve_batch  # noqa: F401
+from .sim3 import Sim3Ransac, Sim3Solver, compute_sim3, solve_batch  # noqa: F401
 
-__all__ = ["ORBextractor", "ORBmatcher", "Sim3Ransac", "Sim3Solver", "compute_stereo_matches", "solve_batch"]
+__all__ = ["ORBextractor", "ORBmatcher", "Sim3Ransac", "Sim3Solver", "compute_sim3", "compute_stereo_matches",
+           "solve_batch"]

@@ -131,6 +131,9 @@ _PROTOS = {
     "orbmi_sim3_iterations": (_i, [_i, _i, C.c_double, _i, C.POINTER(_i)]),
     "orbmi_sim3_sample_triples": (_i, [C.c_uint64, _i, _i, _i, _vp]),
     "orbmi_sim3_max_error": (_i, [_f, C.POINTER(C.c_int32)]),
+    "orbmi_optimize_sim3_batch": (_i, [_vp, _i, _vp, _vp]),
+    "orbmi_search_by_projection_sim3": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _f, C.POINTER(_i)]),
+    "orbmi_debug_sim3_opt_linearize": (_i, [_vp, _vp, _vp, _vp, _vp]),
     "orbmi_slam_create": (_i, [_vp, _i, _vp, C.POINTER(_vp)]),
     "orbmi_slam_destroy": (None, [_vp]),
     "orbmi_slam_wait_local_mapping": (_i, [_vp]),

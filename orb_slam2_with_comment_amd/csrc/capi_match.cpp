@@ -1191,6 +1191,190 @@ int orbmi_search_by_sim3(orbmi_matcher* h, const orbmi_frame_view* kf1, const or
     return finish(m, outs, m.d_scalars, nfound);
 }
 
+int orbmi_search_by_projection_sim3(orbmi_matcher* h, const orbmi_frame_view* kf, const float* Scw, const orbmi_mappoint* mps,
+                                    int n, int32_t* matched, float th, int* nmatches) {
+    if (!h || !kf || !Scw || n < 0 || kf->n < 0 || (n > 0 && !mps) || (kf->n > 0 && !matched) || on_device(Scw) ||
+        on_device(matched))
+        return ORBMI_E_ARG;
+    const int nk = kf->n, cap = Matcher::kCandCap;
+    for (int k = 0; k < nk; k++)
+        if (matched[k] < -2 || matched[k] >= n) return ORBMI_E_ARG;
+    if (nmatches) *nmatches = 0;
+    if (n == 0 || nk == 0) return ORBMI_OK;
+    Matcher& m = h->m;
+    ORBMI_HIP(hipSetDevice(m.device));
+    m.arena_reset();
+    int rc = 0;
+    DevFrame F;
+    if ((rc = make_frame(m, kf, &F, false))) return rc;
+    orbmi::ProjSim3Args a;
+    memset(&a, 0, sizeof(a));
+    // Scw = [sRcw | t]: scw = sqrt(row 0 . row 0) (the dot product in double, rounded to float),
+    // Rcw = sRcw / scw, tcw = t / scw, Ow = -Rcw^T tcw (:368-374), float
+    const float scw = (float)sqrt(((double)Scw[0] * Scw[0] + (double)Scw[1] * Scw[1]) + (double)Scw[2] * Scw[2]);
+    for (int k = 0; k < 12; k++) a.T[k] = Scw[k] / scw;
+    for (int c = 0; c < 3; c++) a.Ow[c] = -((a.T[c] * a.T[3] + a.T[4 + c] * a.T[7]) + a.T[8 + c] * a.T[11]);
+    // spAlreadyFound and the occupied keypoints
+    std::vector<uint8_t> skip((size_t)n, 0), occ((size_t)nk, 0);
+    for (int k = 0; k < nk; k++) {
+        if (matched[k] >= 0) skip[matched[k]] = 1;
+        occ[k] = matched[k] != -1;
+    }
+    a.mps = dev_in(m, mps, (size_t)n, &rc);
+    a.skip = dev_in(m, (const uint8_t*)skip.data(), (size_t)n, &rc);
+    uint8_t* d_occ = (uint8_t*)m.stage((size_t)nk);
+    a.list = (unsigned long long*)m.stage((size_t)n * cap * sizeof(unsigned long long));
+    a.count = (int*)m.stage((size_t)n * sizeof(int));
+    a.best = (unsigned long long*)m.stage((size_t)n * sizeof(unsigned long long));
+    if (rc || !d_occ || !a.list || !a.count || !a.best) return rc ? rc : ORBMI_E_HIP;
+    ORBMI_HIP(m.h2d(d_occ, occ.data(), (size_t)nk));
+    a.occ = d_occ;
+    a.first = 0;
+    a.n = n;
+    a.th = th;
+    ORBMI_HIP(hipMemsetAsync(a.count, 0, (size_t)n * sizeof(int), m.ls()));
+    if ((rc = orbmi::launch_proj_sim3(m, F, a))) return rc;
+    std::vector<unsigned long long> list((size_t)n * cap);
+    std::vector<int> count((size_t)n);
+    ORBMI_HIP(hipMemcpyAsync(count.data(), a.count, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, m.ls()));
+    ORBMI_HIP(hipMemcpyAsync(list.data(), a.list, list.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, m.ls()));
+    ORBMI_HIP(hipStreamSynchronize(m.ls()));
+    // the reference's loop in list order: the best unclaimed keypoint, accepted at <= TH_LOW, which
+    // is the best unclaimed among the candidates <= TH_LOW
+    int found = 0;
+    for (int i = 0; i < n; i++) {
+        if (count[i] == 0) continue;
+        int idx = -1;
+        if (count[i] <= cap) {
+            unsigned long long* L = &list[(size_t)i * cap];
+            std::sort(L, L + count[i]);
+            for (int k = 0; k < count[i] && idx < 0; k++)
+                if (!occ[L[k] & 0xFFFFF]) idx = (int)(L[k] & 0xFFFFF);
+        } else {  // the list overflowed: enumerate this point again against the claims so far
+            orbmi::ProjSim3Args b = a;
+            b.first = i;
+            b.n = 1;
+            ORBMI_HIP(m.h2d(d_occ, occ.data(), (size_t)nk));
+            ORBMI_HIP(hipMemsetAsync(a.count + i, 0, sizeof(int), m.ls()));
+            if ((rc = orbmi::launch_proj_sim3(m, F, b))) return rc;
+            unsigned long long best = ~0ull;
+            ORBMI_HIP(hipMemcpyAsync(&best, a.best + i, sizeof(best), hipMemcpyDeviceToHost, m.ls()));
+            ORBMI_HIP(hipStreamSynchronize(m.ls()));
+            if (best != ~0ull && (int)(best >> 40) <= 50) idx = (int)(best & 0xFFFFF);  // TH_LOW
+        }
+        if (idx < 0) continue;
+        matched[idx] = i;
+        occ[idx] = 1;
+        found++;
+    }
+    if (nmatches) *nmatches = found;
+    return ORBMI_OK;
+}
+
+namespace {
+
+bool sim3_opt_args_ok(const orbmi_sim3_opt_problem& P) {
+    if (P.n < 0) return false;
+    return P.n == 0 || (P.x3d_c1 && P.x3d_c2 && P.obs1 && P.obs2 && P.inv_sigma2_1 && P.inv_sigma2_2);
+}
+
+// Stage one problem; inlier / chi2 are device arrays of n and 2 n entries
+int sim3_opt_stage(Matcher& m, const orbmi_sim3_opt_problem& P, uint8_t* inlier, double* chi2, orbmi::Sim3OptDev* D) {
+    int rc = 0;
+    memset(D, 0, sizeof(*D));
+    const size_t n = (size_t)P.n;
+    D->n = P.n;
+    D->fix_scale = P.fix_scale != 0;
+    D->th2 = P.th2;
+    D->x1 = dev_in(m, P.x3d_c1, 3 * n, &rc);
+    D->x2 = dev_in(m, P.x3d_c2, 3 * n, &rc);
+    D->o1 = dev_in(m, P.obs1, 2 * n, &rc);
+    D->o2 = dev_in(m, P.obs2, 2 * n, &rc);
+    D->w1 = dev_in(m, P.inv_sigma2_1, n, &rc);
+    D->w2 = dev_in(m, P.inv_sigma2_2, n, &rc);
+    memcpy(D->k1, P.k1, sizeof(D->k1));
+    memcpy(D->k2, P.k2, sizeof(D->k2));
+    memcpy(D->R, P.R12, sizeof(D->R));
+    memcpy(D->t, P.t12, sizeof(D->t));
+    D->s = P.s12;
+    D->inlier = inlier;
+    D->chi2 = chi2;
+    return rc;
+}
+
+}  // namespace
+
+int orbmi_optimize_sim3_batch(orbmi_matcher* h, int nproblems, const orbmi_sim3_opt_problem* problems,
+                              orbmi_sim3_opt_result* results) {
+    if (!h || nproblems < 0 || (nproblems > 0 && (!problems || !results))) return ORBMI_E_ARG;
+    for (int k = 0; k < nproblems; k++)
+        if (!sim3_opt_args_ok(problems[k]) || (problems[k].n > 0 && !results[k].inlier)) return ORBMI_E_ARG;
+    if (nproblems == 0) return ORBMI_OK;
+    Matcher& m = h->m;
+    ORBMI_HIP(hipSetDevice(m.device));
+    m.arena_reset();
+    int rc = 0;
+    std::vector<OutBuf> outs;
+    std::vector<orbmi::Sim3OptDev> T((size_t)nproblems);
+    std::vector<orbmi::Sim3OptOut> O((size_t)nproblems);
+    for (int k = 0; k < nproblems; k++) {
+        const size_t n = (size_t)problems[k].n;
+        uint8_t* d_in = n ? dev_out(m, results[k].inlier, n, outs) : (uint8_t*)m.stage(1);
+        double* d_chi = n && results[k].chi2 ? dev_out(m, results[k].chi2, 2 * n, outs)
+                                             : (double*)m.stage(std::max(2 * n, (size_t)1) * sizeof(double));
+        if (!d_in || !d_chi) return ORBMI_E_HIP;
+        if ((rc = sim3_opt_stage(m, problems[k], d_in, d_chi, &T[k]))) return rc;
+    }
+    const orbmi::Sim3OptDev* d_T = dev_in(m, (const orbmi::Sim3OptDev*)T.data(), (size_t)nproblems, &rc);
+    if (rc) return rc;
+    orbmi::Sim3OptOut* d_O = dev_out(m, O.data(), (size_t)nproblems, outs);
+    if (!d_O) return ORBMI_E_HIP;
+    if ((rc = orbmi::launch_sim3_opt(m, nproblems, d_T, d_O))) return rc;
+    if ((rc = finish(m, outs, nullptr, nullptr))) return rc;  // O is host memory: the call has waited
+    for (int k = 0; k < nproblems; k++) {
+        orbmi_sim3_opt_result& R = results[k];
+        memcpy(R.q, O[k].q, sizeof(R.q));
+        memcpy(R.t, O[k].t, sizeof(R.t));
+        R.s = O[k].s;
+        memcpy(R.sR, O[k].sR, sizeof(R.sR));
+        memcpy(R.t_f, O[k].t_f, sizeof(R.t_f));
+        R.n_in = O[k].n_in;
+        R.n_bad = O[k].n_bad;
+        R.iterations[0] = O[k].iterations[0];
+        R.iterations[1] = O[k].iterations[1];
+    }
+    return ORBMI_OK;
+}
+
+int orbmi_debug_sim3_opt_linearize(orbmi_matcher* h, const orbmi_sim3_opt_problem* problem, double* H, double* b,
+                                   double* chi2) {
+    if (!h || !problem || !H || !b || !chi2 || !sim3_opt_args_ok(*problem)) return ORBMI_E_ARG;
+    double lin[57] = {};
+    if (problem->n > 0) {
+        Matcher& m = h->m;
+        ORBMI_HIP(hipSetDevice(m.device));
+        m.arena_reset();
+        int rc = 0;
+        std::vector<OutBuf> outs;
+        const size_t n = (size_t)problem->n;
+        uint8_t* d_in = (uint8_t*)m.stage(n);
+        double* d_chi = (double*)m.stage(2 * n * sizeof(double));
+        if (!d_in || !d_chi) return ORBMI_E_HIP;
+        orbmi::Sim3OptDev T;
+        if ((rc = sim3_opt_stage(m, *problem, d_in, d_chi, &T))) return rc;
+        const orbmi::Sim3OptDev* d_T = dev_in(m, (const orbmi::Sim3OptDev*)&T, 1, &rc);
+        if (rc) return rc;
+        double* d_lin = dev_out(m, (double*)lin, 57, outs);
+        if (!d_lin) return ORBMI_E_HIP;
+        if ((rc = orbmi::launch_sim3_opt_linearize(m, d_T, d_lin))) return rc;
+        if ((rc = finish(m, outs, nullptr, nullptr))) return rc;
+    }
+    memcpy(H, lin, 49 * sizeof(double));
+    memcpy(b, lin + 49, 7 * sizeof(double));
+    *chi2 = lin[56];
+    return ORBMI_OK;
+}
+
 int orbmi_debug_greedy_stats(unsigned long long* out, int reset) {
     if (!out) return ORBMI_E_ARG;
     return orbmi::greedy_stats(out, reset);

@@ -87,6 +87,20 @@ struct Sim3Side {
     int* vn;                     // vnMatch of this direction (n_src)
 };
 
+// SearchByProjection(KF, Scw): the decomposed Scw, the points and the candidate lists
+struct ProjSim3Args {
+    float T[12];                // [Rcw | tcw] = [sRcw | t] / scw
+    float Ow[3];                // -Rcw^T tcw
+    const orbmi_mappoint* mps;
+    const uint8_t* skip;        // per point: spAlreadyFound
+    const uint8_t* occ;         // per keypoint of KF: vpMatched[idx] != NULL (as the replay has it)
+    int first, n;               // the points [first, first + n) of this launch
+    float th;
+    unsigned long long* list;   // per point kCandCap keys (dist << 40 | cell << 20 | idx), unordered
+    int* count;                 // per point: candidates with distance <= TH_LOW (may exceed kCandCap)
+    unsigned long long* best;   // per point: the least key over the unoccupied keypoints (~0: none)
+};
+
 struct Matcher {
     static constexpr int kCandCap = 96;  // candidates kept per query; overflow re-enumerates
     int device = 0;
@@ -203,6 +217,7 @@ int launch_fuse_multi(Matcher& m, int nkf, FuseKF* kfs_host, FuseKF* kfs_dev, co
                       float th, int* best_idx, int* best_dist, int* ncand, int ncap = 0);
 int launch_search_by_sim3(Matcher& m, Sim3Side* sides_host, Sim3Side* sides_dev, int* match12, uint8_t* already2, float th,
                           int* nfound);
+int launch_proj_sim3(Matcher& m, const DevFrame& F, const ProjSim3Args& a);
 int launch_patch_desc(Matcher& m, orbmi_mappoint* mps, const int* desc_from, const uint8_t* desc, int n);
 int greedy_stats(unsigned long long out[5], int reset);
 int greedy_cycles(unsigned long long out[7], int reset);

@@ -2020,6 +2020,82 @@ int launch_search_by_sim3(Matcher& m, Sim3Side* sides_host, Sim3Side* sides_dev,
     return hipGetLastError() == hipSuccess ? ORBMI_OK : ORBMI_E_HIP;
 }
 
+// -------------------------------------------------------------- SearchByProjection(KF, Scw)
+// ORBmatcher::SearchByProjection(KeyFrame*, cv::Mat Scw, vpPoints, vpMatched, th)
+// (src/ORBmatcher.cc:359-479), eight lanes per point as Fuse.  Per point, in the reference's order:
+// bad or already in vpMatched; p3Dc = Rcw Xw + tcw; z < 0; the projection; KeyFrame::IsInImage;
+// dist inside the point's invariance bounds (1.2 mfMaxDistance, 0.8 mfMinDistance: the getters,
+// nothing more); PO . Pn < 0.5 dist; PredictScale; radius = th * scale[level]; GetFeaturesInArea
+// without level limits; occupied keypoints; the octave window [level - 1, level].  The loop is
+// order-dependent (a keypoint taken by an earlier point is skipped by later ones), so the kernel
+// does not decide: it writes every candidate with distance <= TH_LOW (up to kCandCap, in arrival
+// order; the keys order them) and their number, and the least key among the unoccupied
+// keypoints.  The C entry replays the claims in list order; a point whose list overflowed is
+// enumerated again against the occupancy the replay has reached (first / n select it).
+__global__ __launch_bounds__(256) void k_proj_sim3(DevFrame F, const int* __restrict__ cs, const int* __restrict__ cl,
+                                                   ProjSim3Args a) {
+    const int t = blockIdx.x * blockDim.x + threadIdx.x, j = t / kFuseLanes, glane = t % kFuseLanes;
+    const bool valid = j < a.n;  // the other lanes only take part in the group minimum
+    const int i = a.first + (valid ? j : 0);
+    const orbmi_mappoint mp = a.mps[i];
+    bool ok = valid && !(mp.flags & ORBMI_MP_BAD) && !a.skip[i];
+    float Pc[3] = {0, 0, 0};
+    if (ok) {
+        transform(a.T, mp.pos, Pc);
+        ok = !(Pc[2] < 0.0f);
+    }
+    float u = 0, v = 0, dist3D = 0;
+    if (ok) {
+        const float invz = 1.0f / Pc[2];
+        const float x = Pc[0] * invz, y = Pc[1] * invz;
+        u = F.fx * x + F.cx;
+        v = F.fy * y + F.cy;
+        ok = u >= F.min_x && u < F.max_x && v >= F.min_y && v < F.max_y;  // KeyFrame::IsInImage
+    }
+    if (ok) {
+        const float maxDistance = 1.2f * mp.max_distance, minDistance = 0.8f * mp.min_distance;
+        const float PO[3] = {mp.pos[0] - a.Ow[0], mp.pos[1] - a.Ow[1], mp.pos[2] - a.Ow[2]};
+        dist3D = (float)sqrt((double)PO[0] * PO[0] + (double)PO[1] * PO[1] + (double)PO[2] * PO[2]);
+        ok = !(dist3D < minDistance || dist3D > maxDistance);
+        if (ok) {
+            const double dot = (double)PO[0] * mp.normal[0] + (double)PO[1] * mp.normal[1] + (double)PO[2] * mp.normal[2];
+            ok = !(dot < 0.5 * (double)dist3D);
+        }
+    }
+    unsigned long long best = ~0ull;
+    if (ok) {
+        const float ratio = mp.max_distance / dist3D;  // MapPoint::PredictScale(dist, KeyFrame*)
+        int nPredictedLevel = (int)ceilf((float)log((double)ratio) / F.log_scale_factor);
+        if (nPredictedLevel < 0) nPredictedLevel = 0;
+        else if (nPredictedLevel >= F.nlevels) nPredictedLevel = F.nlevels - 1;
+        const float radius = a.th * F.scale[nPredictedLevel];
+        for_features_in_area<kFuseLanes>(F, cs, cl, u, v, radius, -1, -1, glane, [&](int idx, int cell) {
+            if (a.occ[idx]) return;
+            const int kpLevel = F.keys[idx].octave;
+            if (kpLevel < nPredictedLevel - 1 || kpLevel > nPredictedLevel) return;
+            const int d = popc_desc(mp.desc, F.desc + 32 * (long long)idx);
+            const unsigned long long e = cand_entry(d, cell, idx);
+            best = e < best ? e : best;
+            if (d <= TH_LOW) {
+                const int pos = atomicAdd(&a.count[i], 1);  // an integer count; the keys order the list
+                if (pos < Matcher::kCandCap) a.list[(size_t)i * Matcher::kCandCap + pos] = e;
+            }
+        });
+    }
+    best = group_min_u64<kFuseLanes>(best);
+    if (valid && glane == 0) a.best[i] = best;
+}
+
+// a.count[first .. first + n) must be zero (in stream order) before the launch
+int launch_proj_sim3(Matcher& m, const DevFrame& F, const ProjSim3Args& a) {
+    if (F.n > kGreedyMaxKp) return ORBMI_E_UNSUPPORTED;
+    int rc;
+    if ((rc = grid_for(m, F))) return rc;
+    if (a.n > 0)
+        hipLaunchKernelGGL(k_proj_sim3, dim3((a.n * kFuseLanes + 255) / 256), dim3(256), 0, m.ls(), F, m.cur_cs, m.cur_cl, a);
+    return hipGetLastError() == hipSuccess ? ORBMI_OK : ORBMI_E_HIP;
+}
+
 // records whose descriptor was just recomputed (desc_from[i] >= 0: row of `desc`) take it
 __global__ __launch_bounds__(256) void k_patch_desc(orbmi_mappoint* __restrict__ mps, const int* __restrict__ desc_from,
                                                     const uint8_t* __restrict__ desc, int n) {

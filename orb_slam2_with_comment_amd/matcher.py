@@ -138,6 +138,26 @@ class ORBmatcher:
             R.ctypes.data, t.ctypes.data, th, m12.ctypes.data, C.byref(n), vn1.ctypes.data, vn2.ctypes.data))
         return m12[:n1], n.value, vn1[:n1], vn2[:n2]
 
+    def SearchByProjectionSim3(self, kf, Scw, mps, matched, th=10):
+        """SearchByProjection(KeyFrame*, cv::Mat Scw, vpPoints, vpMatched, th)
+        (src/ORBmatcher.cc:359-479): kf is a types.Frame, Scw a 3x4 or 4x4 float matrix [sRcw | t],
+        mps the candidate points (orbmi_mappoint records), matched one entry per keypoint slot of
+        kf as include/orbmi.h codes vpMatched (-1 none, >= 0 the index in mps, -2 a point that is
+        not in mps).  Returns (matched with the new matches, nmatches)."""
+        nk = len(kf.keys)
+        mps = np.ascontiguousarray(mps)
+        if len(matched) != nk:
+            raise ValueError("SearchByProjectionSim3 takes one match per keypoint slot")
+        m = np.zeros(max(nk, 1), np.int32)
+        m[:nk] = matched
+        S = np.ascontiguousarray(np.asarray(Scw, np.float32).reshape(-1, 4)[:3])
+        n = C.c_int()
+        v = kf.view()
+        check("orbmi_search_by_projection_sim3", lib().orbmi_search_by_projection_sim3(
+            self._h, C.addressof(v), S.ctypes.data, mps.ctypes.data if len(mps) else None, len(mps),
+            m.ctypes.data, float(th), C.byref(n)))
+        return m[:nk], n.value
+
     def ComputeDistinctiveDescriptors(self, obs_desc: np.ndarray, obs_off: np.ndarray, desc_out=None):
         """MapPoint::ComputeDistinctiveDescriptors (src/MapPoint.cc:247-316) for a batch of map
         points: rows obs_off[p]..obs_off[p+1] of obs_desc are point p's observation descriptors.

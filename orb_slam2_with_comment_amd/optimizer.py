@@ -199,3 +199,141 @@ def gather_local_ba(pKF: KeyFrame):
             E["ur"][sel] = np.asarray(k.u_right, np.float32)[j]
             E[E.dtype.names[5]][sel] = np.asarray(k.inv_level_sigma2, np.float32)[kp["octave"]]
     return BAProblem(K, P, E), kfs, local_mps
+
+
+class Sim3OptProblem(C.Structure):
+    """orbmi_sim3_opt_problem (include/orbmi.h)."""
+    _fields_ = [("n", C.c_int32), ("x3d_c1", C.c_void_p), ("x3d_c2", C.c_void_p), ("obs1", C.c_void_p),
+                ("obs2", C.c_void_p), ("inv_sigma2_1", C.c_void_p), ("inv_sigma2_2", C.c_void_p),
+                ("k1", C.c_float * 4), ("k2", C.c_float * 4), ("th2", C.c_float), ("fix_scale", C.c_int32),
+                ("R12", C.c_float * 9), ("t12", C.c_float * 3), ("s12", C.c_float)]
+
+
+class Sim3OptResult(C.Structure):
+    """orbmi_sim3_opt_result (include/orbmi.h)."""
+    _fields_ = [("q", C.c_double * 4), ("t", C.c_double * 3), ("s", C.c_double), ("sR", C.c_float * 9),
+                ("t_f", C.c_float * 3), ("n_in", C.c_int32), ("n_bad", C.c_int32), ("iterations", C.c_int32 * 2),
+                ("inlier", C.c_void_p), ("chi2", C.c_void_p)]
+
+
+def sim3_opt_problem(x3d_c1, x3d_c2, obs1, obs2, inv_sigma2_1, inv_sigma2_2, k1, k2, th2, fix_scale, R12, t12, s12) -> dict:
+    """One OptimizeSim3 problem as the arrays orbmi_sim3_opt_problem points to."""
+    f = np.float32
+    return {"x1": np.ascontiguousarray(x3d_c1, f).reshape(-1, 3), "x2": np.ascontiguousarray(x3d_c2, f).reshape(-1, 3),
+            "o1": np.ascontiguousarray(obs1, f).reshape(-1, 2), "o2": np.ascontiguousarray(obs2, f).reshape(-1, 2),
+            "w1": np.ascontiguousarray(inv_sigma2_1, f).reshape(-1), "w2": np.ascontiguousarray(inv_sigma2_2, f).reshape(-1),
+            "k1": np.ascontiguousarray(k1, f).reshape(4), "k2": np.ascontiguousarray(k2, f).reshape(4),
+            "th2": float(f(th2)), "fix_scale": int(bool(fix_scale)), "R12": np.ascontiguousarray(R12, f).reshape(9),
+            "t12": np.ascontiguousarray(t12, f).reshape(3), "s12": float(f(s12))}
+
+
+def _inv_level_sigma2(scale_factors):
+    """mvInvLevelSigma2 (src/ORBextractor.cc:422-436): 1.0f / (scale * scale), float32."""
+    s = np.asarray(scale_factors, np.float32)
+    return (np.float32(1.0) / (s * s).astype(np.float32)).astype(np.float32)
+
+
+class Sim3Optimizer:
+    """Optimizer::OptimizeSim3 (src/Optimizer.cc:1145-1347) on the GPU, batched: one workgroup per
+    problem, every (candidate, hypothesis) pair of LoopClosing::ComputeSim3 in one launch.
+    matcher: an ORBmatcher whose handle, stream and staging arena are used."""
+
+    def __init__(self, matcher=None, device: int = 0):
+        from .matcher import ORBmatcher
+        self._own = matcher is None
+        self.matcher = ORBmatcher(device=device) if matcher is None else matcher
+        self.last = None
+
+    def close(self):
+        if self._own and self.matcher is not None:
+            self.matcher.close()
+        self.matcher = None
+
+    @staticmethod
+    def _fill(P, p):
+        n = len(p["x1"])
+        if any(len(p[k]) != n for k in ("x2", "o1", "o2", "w1", "w2")):
+            raise ValueError("sim3 optimisation arrays differ in length")
+        P.n = n
+        for name, key in (("x3d_c1", "x1"), ("x3d_c2", "x2"), ("obs1", "o1"), ("obs2", "o2"), ("inv_sigma2_1", "w1"),
+                          ("inv_sigma2_2", "w2")):
+            setattr(P, name, p[key].ctypes.data if n else None)
+        P.k1, P.k2 = (C.c_float * 4)(*p["k1"]), (C.c_float * 4)(*p["k2"])
+        P.th2, P.fix_scale = p["th2"], p["fix_scale"]
+        P.R12, P.t12, P.s12 = (C.c_float * 9)(*p["R12"]), (C.c_float * 3)(*p["t12"]), p["s12"]
+        return n
+
+    def run(self, problems: list) -> list:
+        """problems: dicts of sim3_opt_problem().  -> per problem {"q" (x y z w), "t", "s" (doubles),
+        "sR" (3x3), "t_f" (float32, as Converter::toCvMat rounds them), "n_in", "n_bad", "iterations",
+        "inlier" (n, 0 where the reference nulls the match), "chi2" (n, 2)}."""
+        m = len(problems)
+        P, R = (Sim3OptProblem * max(m, 1))(), (Sim3OptResult * max(m, 1))()
+        bufs = []
+        for k, p in enumerate(problems):
+            n = self._fill(P[k], p)
+            b = (np.zeros(max(n, 1), np.uint8), np.zeros((max(n, 1), 2), np.float64))
+            bufs.append(b)
+            R[k].inlier, R[k].chi2 = b[0].ctypes.data, b[1].ctypes.data
+        check("orbmi_optimize_sim3_batch", lib().orbmi_optimize_sim3_batch(self.matcher._h, m, P if m else None, R if m else None))
+        out = []
+        for k, p in enumerate(problems):
+            n = len(p["x1"])
+            out.append({"q": np.array(R[k].q), "t": np.array(R[k].t), "s": float(R[k].s),
+                        "sR": np.array(R[k].sR, np.float32).reshape(3, 3), "t_f": np.array(R[k].t_f, np.float32),
+                        "n_in": R[k].n_in, "n_bad": R[k].n_bad, "iterations": tuple(R[k].iterations),
+                        "inlier": bufs[k][0][:n], "chi2": bufs[k][1][:n]})
+        return out
+
+    def linearize(self, p: dict):
+        """One buildSystem pass at the initial estimate (orbmi_debug_sim3_opt_linearize): H (7x7),
+        b (7), the robust chi2."""
+        P = Sim3OptProblem()
+        self._fill(P, p)
+        H, b, c = np.zeros((7, 7)), np.zeros(7), C.c_double()
+        check("orbmi_debug_sim3_opt_linearize",
+              lib().orbmi_debug_sim3_opt_linearize(self.matcher._h, C.addressof(P), H.ctypes.data, b.ctypes.data, C.byref(c)))
+        return H, b, c.value
+
+    @staticmethod
+    def assemble(kf1, kf2, mps1, mps2, matches1, R12, t12, s12, th2, fix_scale, has_mp1=None):
+        """The reference's assembly loop (:1198-1281) -> (problem dict, vnIndexEdge).  kf1 / kf2:
+        types.Frame; mps1 / mps2: orbmi_mappoint records per keypoint slot; matches1[i] = the KF2
+        slot of vpMatches1[i] (GetIndexInKeyFrame(pKF2)), -1 for a null match, -2 for a point
+        without an index in KF2.  Skipped: a null match, a null or bad pMP1, a bad pMP2, i2 < 0."""
+        from .sim3 import _to_camera
+        from .types import MP_BAD
+        m1 = np.asarray(matches1, np.int64)
+        has1 = np.ones(len(mps1), bool) if has_mp1 is None else np.asarray(has_mp1, bool)
+        keep = []
+        for i in range(len(m1)):
+            i2 = int(m1[i])
+            if i2 == -1:  # !vpMatches1[i]
+                continue
+            if i >= len(mps1) or not has1[i]:  # !pMP1
+                continue
+            if i2 < 0 or i2 >= len(mps2):  # i2 < 0
+                continue
+            if (mps1["flags"][i] & MP_BAD) or (mps2["flags"][i2] & MP_BAD):
+                continue
+            keep.append((i, i2))
+        keep = np.array(keep, np.int64).reshape(-1, 2)
+        i1, i2 = keep[:, 0], keep[:, 1]
+        p = sim3_opt_problem(
+            _to_camera(kf1.tcw, mps1["pos"][i1]), _to_camera(kf2.tcw, mps2["pos"][i2]),
+            np.stack([kf1.keys["x"][i1], kf1.keys["y"][i1]], -1), np.stack([kf2.keys["x"][i2], kf2.keys["y"][i2]], -1),
+            _inv_level_sigma2(kf1.scale_factors)[kf1.keys["octave"][i1]],
+            _inv_level_sigma2(kf2.scale_factors)[kf2.keys["octave"][i2]],
+            [kf1.cam.fx, kf1.cam.fy, kf1.cam.cx, kf1.cam.cy], [kf2.cam.fx, kf2.cam.fy, kf2.cam.cx, kf2.cam.cy],
+            th2, fix_scale, R12, t12, s12)
+        return p, i1.astype(np.int64)
+
+    def OptimizeSim3(self, kf1, kf2, mps1, mps2, matches1, R12, t12, s12, th2, fix_scale, has_mp1=None) -> int:
+        """Optimizer::OptimizeSim3(pKF1, pKF2, vpMatches1, g2oS12, th2, bFixScale): nulls matches1
+        (an integer array, -1 = null) in place where the reference nulls vpMatches1 and returns nIn.
+        The refined g2oS12 and the other outputs of run() are left in self.last."""
+        p, idx = self.assemble(kf1, kf2, mps1, mps2, matches1, R12, t12, s12, th2, fix_scale, has_mp1)
+        r = self.run([p])[0]
+        matches1[idx[r["inlier"] == 0]] = -1
+        self.last = r
+        return r["n_in"]

@@ -260,3 +260,159 @@ def solve_batch(solvers: list, ransac: Sim3Ransac):
         probs.append(s.problem())
     for s, h in zip(solvers, ransac(probs)):
         s.set_hypotheses(h)
+
+
+# ---- LoopClosing::ComputeSim3 from the solvers on (src/LoopClosing.cc:331-490) -------------------
+
+def _quat_to_R(q):
+    x, y, z, w = (float(v) for v in q)
+    tx, ty, tz = 2 * x, 2 * y, 2 * z
+    return np.array([[1 - (ty * y + tz * z), ty * x - tz * w, tz * x + ty * w],
+                     [ty * x + tz * w, 1 - (tx * x + tz * z), tz * y - tx * w],
+                     [tz * x - ty * w, tz * y + tx * w, 1 - (tx * x + ty * y)]], np.float64)
+
+
+class DeviceBackend:
+    """The four device operators compute_sim3 chains, on one matcher handle (one stream, one
+    staging arena).  A test drives compute_sim3 with an object of the same four methods."""
+
+    def __init__(self, matcher=None, device: int = 0):
+        from .matcher import ORBmatcher
+        from .optimizer import Sim3Optimizer
+        self._own = matcher is None
+        self.matcher = ORBmatcher(device=device) if matcher is None else matcher
+        self.ransac = Sim3Ransac(self.matcher)
+        self.optimizer = Sim3Optimizer(self.matcher)
+
+    def close(self):
+        if self._own and self.matcher is not None:
+            self.matcher.close()
+        self.matcher = None
+
+    def solve_batch(self, solvers):
+        solve_batch(solvers, self.ransac)
+
+    def search_by_sim3(self, cur, cand, match12, s, R, t, th):
+        return self.matcher.SearchBySim3(cur["kf"], cur["mps"], cur["has"], cand["kf"], cand["mps"], cand["has"], match12,
+                                         s, R, t, th)[0]
+
+    def optimize(self, problems):
+        return self.optimizer.run(problems)
+
+    def search_by_projection(self, kf, Scw, mps, matched, th):
+        return self.matcher.SearchByProjectionSim3(kf, Scw, mps, matched, th)
+
+
+def compute_sim3(cur_kf, candidates, bow_matches, loop_points_of, fix_scale, seed=0, backend=None):
+    """LoopClosing::ComputeSim3 (src/LoopClosing.cc:331-490) from the Sim3Solvers on, over the
+    device operators.  cur_kf and every candidate: {"kf": types.Frame, "mps": orbmi_mappoint
+    records per keypoint slot, "has": the slot holds a point} (and optionally "bad": isBad());
+    bow_matches[i][j] = the slot in candidate i of SearchByBoW(cur, candidate i)'s match for slot j
+    of the current keyframe, -1 for none (SearchByBoW(KF, KF) is the caller's);
+    loop_points_of(i) -> (records, slot_to_index): mvpLoopMapPoints of candidate i (:436-455) and,
+    per keypoint slot of candidate i, the index of its point in that list (-1: not in it).
+
+    Per round every live candidate runs 5 RANSAC iterations (all hypotheses of all solvers come
+    from one solve_batch call); a candidate at its iteration limit is discarded (bNoMore).  Every
+    candidate that returned a Sim3 goes through SearchBySim3 (th 7.5) and then all of them through
+    one OptimizeSim3 batch (th2 10); the first in candidate order with nIn >= 20 wins, which is the
+    candidate the reference's sequential loop stops at.  Then Scw = Scm * Smw,
+    SearchByProjection(cur, Scw, loop points, th 10), accepted at >= 40 matches.  No SetErase
+    bookkeeping.
+
+    -> {"accepted", "candidate" (index or None), "Scw" (4x4 float32), "scw" {"sR", "t", "s"} in
+    doubles, "matches" (per current slot: the candidate's slot, -1 none), "loop_matched" (per
+    current slot: index into the loop points, -1 none, -2 a point outside the list), "n_total",
+    "log" (per-stage counts)}."""
+    from .optimizer import Sim3Optimizer
+    own = backend is None
+    be = DeviceBackend() if own else backend
+    try:
+        return _compute_sim3(cur_kf, candidates, bow_matches, loop_points_of, fix_scale, seed, be, Sim3Optimizer)
+    finally:
+        if own:
+            be.close()
+
+
+def _compute_sim3(cur, candidates, bow_matches, loop_points_of, fix_scale, seed, be, Sim3Optimizer):
+    n0 = len(candidates)
+    log = []
+    out = {"accepted": False, "candidate": None, "Scw": None, "scw": None, "matches": None, "loop_matched": None,
+           "n_total": 0, "log": log}
+    solvers, discarded = [None] * n0, [False] * n0
+    ncand = 0
+    for i, c in enumerate(candidates):  # :316-348
+        bow = np.asarray(bow_matches[i], np.int32)
+        nmatches = int((bow >= 0).sum())
+        if c.get("bad", False) or nmatches < 20:
+            discarded[i] = True
+            log.append(("discarded", i, nmatches))
+            continue
+        s = Sim3Solver(cur["kf"], c["kf"], cur["mps"], c["mps"], bow, fix_scale, cur["has"], c["has"], seed=seed, solver=i)
+        s.SetRansacParameters(0.99, 20, 300)
+        solvers[i] = s
+        ncand += 1
+    rounds = 0
+    winner = None
+    while ncand > 0 and winner is None:  # :357-423
+        rounds += 1
+        fresh = [s for i, s in enumerate(solvers) if s is not None and not discarded[i] and s._hyp is None
+                 and s.N >= s.mRansacMinInliers]
+        if fresh:
+            be.solve_batch(fresh)
+            log.append(("solve_batch", rounds, len(fresh)))
+        returned = []
+        for i in range(n0):
+            if discarded[i]:
+                continue
+            T, no_more, vb, nin = solvers[i].iterate(5)
+            if no_more:
+                discarded[i] = True
+                ncand -= 1
+            if T is not None:
+                returned.append((i, vb, nin))
+        problems, kept = [], []
+        for i, vb, nin in returned:
+            c, s = candidates[i], solvers[i]
+            bow = np.asarray(bow_matches[i], np.int32)
+            m12 = np.where(vb, bow, -1).astype(np.int32)  # :389-394
+            R, t, sc = s.GetEstimatedRotation(), s.GetEstimatedTranslation(), s.GetEstimatedScale()
+            m12 = np.array(be.search_by_sim3(cur, c, m12, sc, R, t, 7.5), np.int32)
+            p, idx = Sim3Optimizer.assemble(cur["kf"], c["kf"], cur["mps"], c["mps"], m12, R, t, sc, 10, fix_scale, cur["has"])
+            problems.append(p)
+            kept.append((i, m12, idx, nin))
+        if not problems:
+            continue
+        results = be.optimize(problems)
+        log.append(("optimize_batch", rounds, [(i, nin, int((m12 != -1).sum()), r["n_in"]) for (i, m12, _, nin), r in
+                                               zip(kept, results)]))
+        for (i, m12, idx, _), r in zip(kept, results):
+            if r["n_in"] >= 20:  # :408
+                m12[idx[np.asarray(r["inlier"]) == 0]] = -1
+                winner = (i, m12, r)
+                break
+    log.append(("rounds", rounds))
+    if winner is None:
+        return out
+    i, m12, r = winner
+    c = candidates[i]
+    # mg2oScw = gScm * gSmw, gSmw = Sim3(Rmw, tmw, 1.0) (:413-416), then Converter::toCvMat
+    Tmw = np.asarray(c["kf"].tcw, np.float32).reshape(4, 4).astype(np.float64)
+    sR_cm = float(r["s"]) * _quat_to_R(r["q"])
+    sR = sR_cm @ Tmw[:3, :3]
+    t = sR_cm @ Tmw[:3, 3] + np.asarray(r["t"], np.float64)
+    Scw = np.eye(4, dtype=np.float32)
+    Scw[:3, :3], Scw[:3, 3] = sR.astype(np.float32), t.astype(np.float32)
+    pts, slot_to_index = loop_points_of(i)
+    slot_to_index = np.asarray(slot_to_index, np.int64)
+    matched = np.full(len(m12), -1, np.int32)  # mvpCurrentMatchedPoints in the list's indices
+    has = m12 >= 0
+    where = slot_to_index[m12[has]]
+    matched[has] = np.where(where >= 0, where, -2)
+    matched[m12 == -2] = -2
+    matched, nproj = be.search_by_projection(cur["kf"], Scw, pts, matched, 10)
+    n_total = int((np.asarray(matched) != -1).sum())
+    log.append(("search_by_projection", i, int(nproj), n_total))
+    out.update(candidate=i, Scw=Scw, scw={"sR": sR, "t": t, "s": float(r["s"])}, matches=m12,
+               loop_matched=np.asarray(matched, np.int32), n_total=n_total, accepted=n_total >= 40)
+    return out

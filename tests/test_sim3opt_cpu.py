@@ -1,0 +1,494 @@
+"""OptimizeSim3 without a GPU: the numpy restatement's self-checks (tests/sim3opt_reference.py),
+the host build of csrc/sim3_opt.h against it, the Python assembly rules of
+optimizer.Sim3Optimizer.OptimizeSim3 and the control flow of sim3.compute_sim3 over a fake
+backend."""
+import functools
+import os
+import shutil
+import struct
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import sim3opt_reference as ref  # noqa: E402
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+POSE_TOL = 1e-4  # the GPU bars, which the host build of the same header has to meet as well
+
+
+@functools.lru_cache(maxsize=None)
+def solved(spec, mode="numeric"):
+    return ref.optimize_sim3(ref.problem(spec), mode)
+
+
+@functools.lru_cache(maxsize=None)
+def qualified(spec):
+    return ref.qualifies(ref.problem(spec))
+
+
+# ---- the restatement's self-checks ----------------------------------------------------------------
+
+def test_sim3_exp_is_a_similarity_and_inverse_inverts():
+    rng = np.random.default_rng(0)
+    for u in (rng.normal(0, 0.3, 7), [1e-9, 0, 0, 0, 0, 0, 0], [0, 0, 0, 0.1, 0.2, 0.3, 1e-7], [0.2, -0.1, 0.3, 1, 2, 3, 0]):
+        S = ref.sim3_exp(u)
+        R = ref.quat_to_R(S.q)
+        assert np.abs(R @ R.T - np.eye(3)).max() < 1e-12 or np.linalg.norm(u[:3]) < 1e-5
+        x = rng.normal(0, 1, (5, 3))
+        back = S.inverse().map(S.map(x))
+        assert np.abs(back - x).max() < 1e-12
+        assert abs(float(S.s) - np.exp(u[6])) < 1e-15
+    # the product composes the maps
+    A, B = ref.sim3_exp(rng.normal(0, 0.3, 7)), ref.sim3_exp(rng.normal(0, 0.3, 7))
+    x = rng.normal(0, 1, (4, 3))
+    assert np.abs(A.mul(B).map(x) - A.map(B.map(x))).max() < 1e-12
+
+
+@pytest.mark.parametrize("fix_scale", [0, 1])
+def test_analytic_and_numeric_jacobians_agree(fix_scale):
+    P = ref.make_problem(100 + fix_scale, 40, fix_scale, 0.1)
+    o = ref._Opt(P, "numeric")
+    S = P.initial()
+    Jn, Ja = o.jacobians(S, "numeric"), o.jacobians(S, "analytic")
+    for n_, a_ in zip(Jn, Ja):
+        scale = np.abs(a_).max()
+        # differencing noise: |e| ulp / (2 delta) ~ 500 * 1.1e-16 / 2e-9 ~ 3e-5 per evaluation
+        assert np.abs(n_ - a_).max() < 2e-3, np.abs(n_ - a_).max()
+        assert np.abs(n_ - a_).max() / scale < 1e-5
+    Hn, bn, cn = o.build(S, "numeric")
+    Ha, ba, ca = o.build(S, "analytic")
+    assert np.abs(Hn - Ha).max() / np.abs(Ha).max() < 1e-6
+    assert np.abs(bn - ba).max() / np.abs(ba).max() < 1e-6
+    assert cn == ca
+
+
+def test_fix_scale_zeroes_column_six():
+    P = ref.make_problem(7, 50, 1, 0.1)
+    for mode in ("numeric", "analytic"):
+        H, b, _ = ref.linearize(P, mode)
+        assert (H[6, :] == 0).all() and (H[:, 6] == 0).all() and b[6] == 0
+    r = solved((7, 65, 1, 0.15))
+    assert r.s == np.float64(ref.problem((7, 65, 1, 0.15)).s12)
+    H, b, _ = ref.linearize(ref.make_problem(7, 50, 0, 0.1))
+    assert H[6, 6] > 0 and b[6] != 0
+
+
+def test_every_committed_problem_qualifies():
+    spreads = {}
+    for spec in ref.PROBLEMS:
+        ok, spread = qualified(spec)
+        spreads[spec] = spread
+        assert ok, (spec, spread)
+    print("numeric-versus-analytic spread of sR, t, s:", {k: f"{v:.2e}" for k, v in spreads.items()})
+    print("max", max(spreads.values()))
+
+
+def test_committed_problems_cover_both_iteration_choices_and_the_sizes():
+    ns = {s[1] for s in ref.PROBLEMS}
+    assert {0, 9, 10, 63, 64, 65, 257} <= ns
+    assert {s[2] for s in ref.PROBLEMS} == {0, 1}
+    more = {solved(s).more_iterations for s in ref.PROBLEMS if s[1] >= 10}
+    assert more == {5, 10}
+    for s in ref.PROBLEMS:
+        r = solved(s)
+        P = ref.problem(s)
+        assert r.more_iterations == (10 if r.n_bad > 0 else 5)
+        if not r.early:
+            # the outliers the scene planted are the pairs the two passes remove
+            planted = np.zeros(P.n, bool)
+            planted[P.truth["outliers"]] = True
+            assert (r.inlier[planted] == 0).all()
+            assert r.n_in >= P.n - len(P.truth["outliers"]) - 3
+            assert r.n_in == int(r.inlier.sum())
+
+
+def test_early_return_at_nine_and_continuation_at_ten():
+    # 12 pairs: 3 gross outliers leave 9 (return 0, the estimate as passed in), 2 leave 10
+    for k, early in ((3, True), (2, False)):
+        P = ref.make_problem(40 + k, 12, 0, 0.0, n_outliers=k)
+        r = ref.optimize_sim3(P)
+        assert r.n_bad == k, (k, r.n_bad)
+        assert r.early == early
+        if early:
+            assert r.n_in == 0 and r.iterations[1] == 0
+            assert r.S.bits() == P.initial().bits()
+            assert int(r.inlier.sum()) == 12 - k  # what the first pass nulled stays nulled
+        else:
+            assert r.n_in == 10 and r.iterations[1] > 0 and r.more_iterations == 10
+            assert r.S.bits() != P.initial().bits()
+
+
+def test_five_more_iterations_without_outliers():
+    r = solved((6, 65, 0, 0.0))
+    assert r.n_bad == 0 and r.more_iterations == 5 and r.iterations[1] <= 5
+    r = solved((4, 63, 0, 0.15))
+    assert r.n_bad > 0 and r.more_iterations == 10
+
+
+def test_optimisation_recovers_the_scene():
+    for spec in ((8, 257, 0, 0.15), (9, 257, 1, 0.0)):
+        P, r = ref.problem(spec), solved(spec)
+        T = P.truth
+        assert np.abs(r.sR - T["s"] * T["R"]).max() < 5e-3
+        assert np.abs(r.t - T["t"]).max() < 2e-2
+        e0 = np.abs(P.initial().matrix()[0] - T["s"] * T["R"]).max()
+        assert np.abs(r.sR - T["s"] * T["R"]).max() < e0
+
+
+def test_nan_estimate_and_zero_depth_terminate():
+    P = ref.make_problem(5, 30, 0, 0.1)
+    P.t12[0] = np.nan
+    r = ref.optimize_sim3(P)
+    assert r.n_in == 0 and r.n_bad == 30
+    P = ref.make_problem(5, 30, 0, 0.1)
+    P.x3d_c1[3, 2] = 0.0
+    r = ref.optimize_sim3(P)
+    assert r.inlier[3] == 0
+
+
+# ---- the host build of csrc/sim3_opt.h ------------------------------------------------------------
+
+def write_problem(P, path):
+    with open(path, "wb") as f:
+        f.write(struct.pack("<ii", P.n, P.fix_scale))
+        f.write(np.concatenate([[P.th2], P.k1, P.k2, P.R12.reshape(9), P.t12, [P.s12]]).astype("<f4").tobytes())
+        for a in (P.x3d_c1, P.x3d_c2, P.obs1, P.obs2, P.inv_sigma2_1, P.inv_sigma2_2):
+            f.write(np.ascontiguousarray(a, "<f4").tobytes())
+
+
+def read_check_output(path, n):
+    b = open(path, "rb").read()
+    o, out = 0, {}
+    for name, dt, cnt in (("head", "<f8", 8), ("sR_f", "<f4", 9), ("t_f", "<f4", 3), ("cnt", "<i4", 4), ("inlier", "u1", n),
+                          ("chi2", "<f8", 2 * n), ("lin", "<f8", 57)):
+        a = np.frombuffer(b, dt, cnt, o)
+        o += a.nbytes
+        out[name] = a
+    assert o == len(b)
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def check_program(sanitize=False):
+    cxx = shutil.which("c++") or shutil.which("g++") or shutil.which("clang++")
+    if not cxx:
+        pytest.fail("no host C++ compiler")
+    import tempfile
+    d = tempfile.mkdtemp(prefix="sim3opt_check_")
+    exe = os.path.join(d, "sim3opt_check")
+    cmd = [cxx, "-O2", "-std=c++17", "-ffp-contract=off", "-I", os.path.join(ROOT, "orb_slam2_with_comment_amd", "csrc"),
+           os.path.join(ROOT, "tests", "cpp", "sim3opt_check.cpp"), "-o", exe]
+    if sanitize:
+        cmd[1:1] = ["-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"]
+    subprocess.run(cmd, check=True)
+    return exe
+
+
+def run_check(P, sanitize=False):
+    exe = check_program(sanitize)
+    d = os.path.dirname(exe)
+    inp, out = os.path.join(d, "in.bin"), os.path.join(d, "out.bin")
+    write_problem(P, inp)
+    subprocess.run([exe, inp, out], check=True, capture_output=True)
+    return read_check_output(out, P.n)
+
+
+def compare_with_restatement(P, r, got, lin_ref, lin_spread):
+    """The GPU bars (the issue's "Parity"), applied to a result dict (head, sR_f, t_f, cnt, inlier,
+    lin) against the numeric restatement r.  Returns the largest transform deviation."""
+    assert got["cnt"][0] == r.n_in and got["cnt"][1] == r.n_bad, (got["cnt"], r.n_in, r.n_bad)
+    assert (got["inlier"] == r.inlier).all()
+    q, t, s = got["head"][:4], got["head"][4:7], got["head"][7]
+    sR = s * ref.quat_to_R(q)
+    dev = max(np.abs(sR - r.sR).max(), np.abs(t - r.t).max(), abs(s - r.s))
+    dev_f = max(np.abs(got["sR_f"].reshape(3, 3).astype(np.float64) - r.sR_f.astype(np.float64)).max(),
+                np.abs(got["t_f"].astype(np.float64) - r.t_f.astype(np.float64)).max())
+    assert dev <= POSE_TOL and dev_f <= POSE_TOL, (dev, dev_f)
+    if P.fix_scale:
+        assert s == np.float64(P.s12)
+    if r.early:
+        assert got["head"].tobytes() == r.S.bits()
+    if P.n:
+        H, b, chi = got["lin"][:49].reshape(7, 7), got["lin"][49:56], got["lin"][56]
+        Hr, br, cr = lin_ref
+        print("linearisation: max|dH|/max|H| %.2e (numeric-versus-analytic %.2e), max|db|/max|b| %.2e (%.2e), chi2 rel %.1e"
+              % (np.abs(H - Hr).max() / np.abs(Hr).max(), lin_spread[0], np.abs(b - br).max() / np.abs(br).max(), lin_spread[1],
+                 abs(chi - cr) / abs(cr)))
+        assert np.abs(H - Hr).max() / np.abs(Hr).max() <= 2 * lin_spread[0], (np.abs(H - Hr).max() / np.abs(Hr).max(), lin_spread)
+        assert np.abs(b - br).max() / np.abs(br).max() <= 2 * lin_spread[1]
+        assert abs(chi - cr) <= 1e-9 * abs(cr)
+        if P.fix_scale:
+            assert (H[6, :] == 0).all() and (H[:, 6] == 0).all() and b[6] == 0
+    return float(dev)
+
+
+@functools.lru_cache(maxsize=None)
+def linearisation(spec):
+    """The numeric restatement's H, b, chi2 at the initial estimate of a committed problem, and
+    its own numeric-versus-analytic figures max|dH| / max|H|, max|db| / max|b|."""
+    P = ref.problem(spec)
+    Hn, bn, cn = ref.linearize(P, "numeric")
+    Ha, ba, _ = ref.linearize(P, "analytic")
+    return (Hn, bn, cn), (np.abs(Hn - Ha).max() / np.abs(Ha).max(), np.abs(bn - ba).max() / np.abs(ba).max())
+
+
+def test_host_header_meets_the_gpu_bars():
+    worst = 0.0
+    for spec in ref.PROBLEMS:
+        P, r = ref.problem(spec), solved(spec)
+        got = run_check(P)
+        lin_ref, lin_spread = linearisation(spec) if P.n else (None, None)
+        worst = max(worst, compare_with_restatement(P, r, got, lin_ref, lin_spread))
+    print("host header versus restatement, max |d(sR, t, s)|:", worst)
+
+
+def test_host_header_under_sanitizers():
+    """The stand-alone check program with -fsanitize=address,undefined, on its own."""
+    for spec in ((4, 63, 0, 0.15), (1, 0, 0, 0.0), (2, 9, 0, 0.0)):
+        P = ref.problem(spec)
+        got = run_check(P, sanitize=True)
+        assert got["cnt"][0] == solved(spec).n_in
+
+
+# ---- the Python assembly of OptimizeSim3 ----------------------------------------------------------
+
+def _two_keyframes(n=40, seed=3):
+    """Two types.Frame keyframes whose slot i holds the same world point, from a committed-style
+    scene: the assembly must reproduce the scene's arrays."""
+    from orb_slam2_with_comment_amd import synth
+    from orb_slam2_with_comment_amd.types import KP_DTYPE, MAPPOINT_DTYPE, Frame
+    import dataclasses
+    P = ref.make_problem(seed, n, 0, 0.1)
+    rng = np.random.default_rng(seed)
+    scales, inv = ref.level_tables()
+    frames, maps = [], []
+    for x3d, obs, w, k in ((P.x3d_c1, P.obs1, P.inv_sigma2_1, P.k1), (P.x3d_c2, P.obs2, P.inv_sigma2_2, P.k2)):
+        keys = np.zeros(n, KP_DTYPE)
+        keys["x"], keys["y"] = obs[:, 0], obs[:, 1]
+        keys["octave"] = [int(np.nonzero(inv == v)[0][0]) for v in w]
+        cam = dataclasses.replace(synth.KITTI, fx=float(k[0]), fy=float(k[1]), cx=float(k[2]), cy=float(k[3]))
+        tcw = np.eye(4, dtype=np.float32)
+        tcw[:3, 3] = rng.normal(0, 1, 3).astype(np.float32)
+        frames.append(Frame(keys, np.zeros((n, 32), np.uint8), np.full(n, -1, np.float32), tcw, cam, scales))
+        mp = np.zeros(n, MAPPOINT_DTYPE)
+        mp["pos"] = x3d - tcw[:3, 3]  # identity rotation: Rcw X + tcw gives x3d back to rounding
+        maps.append(mp)
+    return P, frames, maps
+
+
+def test_assembly_rules_of_optimize_sim3():
+    from orb_slam2_with_comment_amd.optimizer import Sim3Optimizer
+    from orb_slam2_with_comment_amd.types import MP_BAD
+    P, (kf1, kf2), (mps1, mps2) = _two_keyframes()
+    n = P.n
+    matches = np.arange(n, dtype=np.int32)[::-1].copy()  # slot i of KF1 <-> slot n - 1 - i of KF2
+    kf2.keys[:] = kf2.keys[::-1]
+    mps2[:] = mps2[::-1]
+    has1 = np.ones(n, np.uint8)
+    matches[2] = -1          # a null match
+    has1[4] = 0              # a null pMP1
+    mps1["flags"][6] |= MP_BAD
+    mps2["flags"][matches[8]] |= MP_BAD
+    matches[10] = -2         # a point without an index in KF2: i2 < 0
+    p, idx = Sim3Optimizer.assemble(kf1, kf2, mps1, mps2, matches, P.R12, P.t12, P.s12, 10, 0, has1)
+    keep = np.array([i for i in range(n) if i not in (2, 4, 6, 8, 10)])
+    assert idx.tolist() == keep.tolist()
+    np.testing.assert_array_equal(p["o1"], P.obs1[keep])
+    np.testing.assert_array_equal(p["o2"], P.obs2[keep])
+    np.testing.assert_array_equal(p["w1"], P.inv_sigma2_1[keep])
+    np.testing.assert_array_equal(p["w2"], P.inv_sigma2_2[keep])
+    np.testing.assert_allclose(p["x1"], P.x3d_c1[keep], atol=2e-6)
+    np.testing.assert_allclose(p["x2"], P.x3d_c2[keep], atol=2e-6)
+    np.testing.assert_array_equal(p["k1"], P.k1)
+    np.testing.assert_array_equal(p["k2"], P.k2)
+    assert p["th2"] == 10.0 and p["fix_scale"] == 0 and p["s12"] == float(P.s12)
+
+    class Fake(Sim3Optimizer):  # the device call replaced by the restatement
+        def __init__(self):
+            self.last = None
+
+        def run(self, problems):
+            out = []
+            for q in problems:
+                r = ref.optimize_sim3(ref.Problem(q["x1"], q["x2"], q["o1"], q["o2"], q["w1"], q["w2"], q["k1"], q["k2"],
+                                                  q["th2"], q["fix_scale"], q["R12"], q["t12"], q["s12"]))
+                out.append({"n_in": r.n_in, "inlier": r.inlier})
+            return out
+
+    before = matches.copy()
+    n_in = Fake().OptimizeSim3(kf1, kf2, mps1, mps2, matches, P.R12, P.t12, P.s12, 10, 0, has1)
+    nulled = np.nonzero(matches != before)[0]
+    assert n_in == len(keep) - len(nulled) > 20 and len(nulled) > 0
+    assert set(nulled) <= set(keep) and (matches[nulled] == -1).all()  # skipped matches stay as they were
+
+
+# ---- the driver's control flow over a fake backend -------------------------------------------------
+
+class ScriptedBackend:
+    """Returns what the script says and records the calls."""
+
+    def __init__(self, n_in, nproj_total):
+        self.n_in, self.nproj_total, self.calls = n_in, nproj_total, []
+
+    def solve_batch(self, solvers):
+        import sim3_reference as R
+        self.calls.append(("solve_batch", [s.solver for s in solvers]))
+        for s in solvers:
+            tri = R.sample_triples(s.seed, s.solver, s.N, s.mRansacMaxIts)
+            s.set_hypotheses(R.hypotheses(s.mvX3Dc1, s.mvX3Dc2, s.mvnMaxError1, s.mvnMaxError2, s.mK1, s.mK2,
+                                          int(s.mbFixScale), tri))
+
+    def search_by_sim3(self, cur, cand, match12, s, R, t, th):
+        self.calls.append(("search_by_sim3", cand["name"], th))
+        return match12
+
+    def optimize(self, problems):
+        self.calls.append(("optimize", len(problems)))
+        out = []
+        for p in problems:
+            n_in = self.n_in[len(p["x1"])]
+            out.append({"n_in": n_in, "inlier": (np.arange(len(p["x1"])) < n_in).astype(np.uint8), "q": [0, 0, 0, 1.0],
+                        "t": [0, 0, 0.0], "s": 1.0})
+        return out
+
+    def search_by_projection(self, kf, Scw, mps, matched, th):
+        self.calls.append(("search_by_projection", th))
+        m = np.asarray(matched).copy()
+        free = np.nonzero(m == -1)[0][:max(self.nproj_total - int((m != -1).sum()), 0)]
+        m[free] = 0
+        return m, len(free)
+
+
+def _driver_inputs():
+    """The current keyframe and three candidates over one two-camera scene: candidate 0 has 15 BoW
+    matches (discarded), candidate 1 has shuffled correspondences (RANSAC never returns), and
+    candidates 2 and 3 are true loops with 60 and 50 matches."""
+    P, (kf1, kf2), (mps1, mps2) = _two_keyframes(n=60, seed=8)
+    cur = {"kf": kf1, "mps": mps1, "has": np.ones(60, np.uint8)}
+    rng = np.random.default_rng(0)
+    cands, bows = [], []
+    for name, keep, shuffle in (("few", 15, False), ("shuffled", 60, True), ("loop60", 60, False), ("loop50", 50, False)):
+        cands.append({"kf": kf2, "mps": mps2, "has": np.ones(60, np.uint8), "name": name})
+        b = np.arange(60, dtype=np.int32)
+        if shuffle:
+            b = rng.permutation(60).astype(np.int32)
+        b[keep:] = -1
+        bows.append(b)
+    return cur, cands, bows
+
+
+def test_driver_control_flow():
+    from orb_slam2_with_comment_amd.sim3 import compute_sim3
+    cur, cands, bows = _driver_inputs()
+
+    def loop_points_of(i):
+        return cands[i]["mps"], np.arange(60)
+
+    # both true loops return a Sim3 in round 1; 60 pairs give nIn 10 (< 20), 50 pairs 25: the later wins
+    be = ScriptedBackend({60: 10, 50: 25}, 45)
+    r = compute_sim3(cur, cands, bows, loop_points_of, False, seed=1, backend=be)
+    assert r["accepted"] and r["candidate"] == 3 and r["n_total"] == 45
+    assert be.calls[0] == ("solve_batch", [1, 2, 3])  # candidate 0 never got a solver; one batch per round
+    assert [c for c in be.calls if c[0] == "search_by_sim3"][:2] == [("search_by_sim3", "loop60", 7.5), ("search_by_sim3", "loop50", 7.5)]
+    assert ("optimize", 2) in be.calls and be.calls[-1] == ("search_by_projection", 10)
+    assert sum(c[0] == "solve_batch" for c in be.calls) == 1
+    assert ("discarded", 0, 15) in r["log"]
+    assert (r["matches"][:25] == np.arange(25)).all() and (r["matches"][25:] == -1).all()  # what OptimizeSim3 nulled
+    # the first in candidate order wins when both pass
+    be = ScriptedBackend({60: 30, 50: 25}, 45)
+    assert compute_sim3(cur, cands, bows, loop_points_of, False, seed=1, backend=be)["candidate"] == 2
+    # 39 matches after the projection search: the loop is rejected, the candidate is still reported
+    be = ScriptedBackend({60: 30, 50: 25}, 39)
+    r = compute_sim3(cur, cands[:3], bows[:3], loop_points_of, False, seed=1, backend=be)
+    assert not r["accepted"] and r["candidate"] == 2 and r["n_total"] == 39
+    # nobody reaches 20 inliers: every candidate runs out of iterations (bNoMore) and the loop ends
+    be = ScriptedBackend({60: 10, 50: 10}, 45)
+    r = compute_sim3(cur, cands, bows, loop_points_of, False, seed=1, backend=be)
+    assert not r["accepted"] and r["candidate"] is None
+    assert not any(c[0] == "search_by_projection" for c in be.calls)
+    # only the shuffled candidate: RANSAC never returns a Sim3, nothing is optimised
+    be = ScriptedBackend({60: 30}, 45)
+    r = compute_sim3(cur, cands[:2], bows[:2], loop_points_of, False, seed=1, backend=be)
+    assert not r["accepted"] and not any(c[0] == "optimize" for c in be.calls)
+
+
+# ---- the driver over the numpy restatements (what the GPU end-to-end case is compared with) --------
+
+class RestatementBackend:
+    """compute_sim3's four operators from the numpy restatements."""
+
+    def solve_batch(self, solvers):
+        import sim3_reference as R
+        for s in solvers:
+            if s.triples is None:
+                s.triples = R.sample_triples(s.seed, s.solver, s.N, s.mRansacMaxIts)
+            s.set_hypotheses(R.hypotheses(s.mvX3Dc1, s.mvX3Dc2, s.mvnMaxError1, s.mvnMaxError2, s.mK1, s.mK2,
+                                          int(s.mbFixScale), s.triples))
+
+    def search_by_sim3(self, cur, cand, match12, s, R12, t12, th):
+        import sim3_reference as R
+        return R.search_by_sim3(cur["kf"], cur["mps"], cur["has"], cand["kf"], cand["mps"], cand["has"], s, R12, t12, th,
+                                match12)[2]
+
+    def optimize(self, problems):
+        out = []
+        for q in problems:
+            r = ref.optimize_sim3(ref.Problem(q["x1"], q["x2"], q["o1"], q["o2"], q["w1"], q["w2"], q["k1"], q["k2"],
+                                              q["th2"], q["fix_scale"], q["R12"], q["t12"], q["s12"]))
+            out.append({"n_in": r.n_in, "n_bad": r.n_bad, "inlier": r.inlier, "q": r.S.q, "t": r.S.t, "s": float(r.S.s)})
+        return out
+
+    def search_by_projection(self, kf, Scw, mps, matched, th):
+        return ref.search_by_projection_sim3(kf, Scw, mps, matched, th)
+
+
+@functools.lru_cache(maxsize=None)
+def driver_scene():
+    """Keyframes 4 (current) and 6 (the loop candidate) of the synthetic sequence
+    (sim3_reference.sim3_search_scene): the BoW matches are the mutual matches of SearchBySim3
+    under the true transform, thinned to every second one; candidate 0 has them shuffled among
+    themselves, candidate 1 has them as they are.  The loop points are the candidate's own map
+    points."""
+    import sim3_reference as R
+    sc = R.sim3_search_scene(4, 6, 1.0)
+    none = np.full(len(sc["kf1"].keys), -1, np.int32)
+    m12 = R.search_by_sim3(sc["kf1"], sc["mps1"], sc["has1"], sc["kf2"], sc["mps2"], sc["has2"], 1.0, sc["R12"], sc["t12"],
+                           7.5, none)[2]
+    slots = np.nonzero(m12 >= 0)[0][::2]
+    true = none.copy()
+    true[slots] = m12[slots]
+    shuffled = none.copy()
+    shuffled[slots] = np.random.default_rng(5).permutation(m12[slots])
+    cur = {"kf": sc["kf1"], "mps": sc["mps1"], "has": sc["has1"]}
+    cand = {"kf": sc["kf2"], "mps": sc["mps2"], "has": sc["has2"]}
+    has2 = sc["has2"] == 1
+    slot_to_index = np.where(has2, np.cumsum(has2) - 1, -1)
+    pts = sc["mps2"][has2]
+    return cur, [cand, cand], [shuffled, true], (lambda i: (pts, slot_to_index)), len(slots)
+
+
+@functools.lru_cache(maxsize=None)
+def driver_restatement():
+    from orb_slam2_with_comment_amd.sim3 import compute_sim3
+    cur, cands, bows, loop_points_of, _ = driver_scene()
+    return compute_sim3(cur, cands, bows, loop_points_of, True, seed=7, backend=RestatementBackend())
+
+
+def test_driver_over_the_restatements_accepts_the_true_loop(oracle):
+    cur, cands, bows, _, nbow = driver_scene()
+    r = driver_restatement()
+    print("driver log", r["log"])
+    assert nbow >= 40
+    assert r["accepted"] and r["candidate"] == 1 and r["n_total"] >= 40
+    # Scw = Scm Smw is the current keyframe's pose (the map is one world, scale 1)
+    T = np.asarray(cur["kf"].tcw, np.float64).reshape(4, 4)
+    assert np.abs(r["Scw"][:3, :3] - T[:3, :3]).max() < 5e-3
+    assert np.abs(r["Scw"][:3, 3] - T[:3, 3]).max() < 0.1
+    # the shuffled candidate alone is rejected
+    from orb_slam2_with_comment_amd.sim3 import compute_sim3
+    cur, cands, bows, loop_points_of, _ = driver_scene()
+    r0 = compute_sim3(cur, cands[:1], bows[:1], loop_points_of, True, seed=7, backend=RestatementBackend())
+    assert not r0["accepted"] and r0["candidate"] is None
