@@ -299,6 +299,19 @@ int orbmi_search_by_bow(orbmi_matcher* m, const orbmi_frame_view* KF, const uint
                         const orbmi_feature_vector* f_fv, float nnratio, int check_ori, int32_t* match_kf,
                         int* nmatches);
 
+/* ORBmatcher::SearchByBoW(KeyFrame* pKF1, KeyFrame* pKF2, vector<MapPoint*>& vpMatches12)
+ * (src/ORBmatcher.cc:635-768), the form LoopClosing::ComputeSim3 calls (src/LoopClosing.cc:330).
+ * ok1[j] / ok2[j] = the keyframe's GetMapPointMatches()[j] && !isBad() (both sides need a live
+ * point, :671-675 and :687-693); fv1 / fv2 = the keyframes' mFeatVec; keys_un supply mvKeysUn's
+ * angles.  Unlike the (KeyFrame, Frame) form a match needs bestDist1 < TH_LOW strictly (:711), and
+ * the result is indexed by KF1's keypoint: match12[i1] (KF1.n entries, at least one) = the KF2
+ * keypoint whose map point vpMatches12[i1] is, else -1.  This is the bow_matches row
+ * compute_sim3 takes.  *nmatches = the return value.  n_device views are not accepted. */
+int orbmi_search_by_bow_kf(orbmi_matcher* m, const orbmi_frame_view* KF1, const uint8_t* ok1,
+                           const orbmi_feature_vector* fv1, const orbmi_frame_view* KF2, const uint8_t* ok2,
+                           const orbmi_feature_vector* fv2, float nnratio, int check_ori, int32_t* match12,
+                           int* nmatches);
+
 /* ORBmatcher::SearchForTriangulation(KeyFrame* pKF1, KeyFrame* pKF2, cv::Mat F12,
  * vector<pair<size_t,size_t>>& vMatchedPairs, bool bOnlyStereo) (src/ORBmatcher.cc:783-975)
  * with CheckDistEpipolarLine (:173-196): KF1 / KF2 views need keys_un, u_right, desc, tcw, the
@@ -1004,6 +1017,71 @@ typedef struct orbmi_sim3_opt_result {
  * anything is launched: a NULL table, n < 0, a NULL array of a problem with n > 0. */
 int orbmi_optimize_sim3_batch(orbmi_matcher* m, int nproblems, const orbmi_sim3_opt_problem* problems,
                               orbmi_sim3_opt_result* results);
+
+/* ---- LoopClosing::DetectLoop: the KeyFrameDatabase ----------------------------------- */
+
+/* KeyFrameDatabase (src/KeyFrameDatabase.cc:33-197) restated forward: instead of the inverted
+ * file (one std::list<KeyFrame*> per word) every keyframe's BowVector sits in a slot of one
+ * device arena, word ids ascending, and a query intersects the query vector with every indexed
+ * slot at once.  Slots are numbered in the order of orbmi_kfdb_store.  `scoring` is DBoW2's
+ * ScoringType (BowVector.h:45-53): L1_NORM (0) and L2_NORM (1), else ORBMI_E_UNSUPPORTED.
+ * max_keyframes slots and max_words_total words are allocated here; a store beyond either
+ * returns ORBMI_E_CAP.  Keyframe ids are in [0, 2^24).  Calls on one handle are serialised. */
+typedef struct orbmi_kfdb orbmi_kfdb;
+int orbmi_kfdb_create(int device, int scoring, int max_keyframes, int max_words_total, orbmi_kfdb** out);
+void orbmi_kfdb_destroy(orbmi_kfdb* db);
+/* KeyFrameDatabase::clear (:69-73) and the stored vectors with it: no slot is left. */
+int orbmi_kfdb_clear(orbmi_kfdb* db);
+/* Copy keyframe kf_id's mBowVec (n words ascending, n <= 8192, host or device arrays) into the
+ * arena.  A host vector that is not strictly ascending returns ORBMI_E_ARG; for a device vector
+ * (orbmi_transform's device outputs, ready on the device when the call is made) ascending order
+ * is a precondition: a violation gives wrong counts, never an access outside the vector.  An id
+ * stored before returns ORBMI_E_STATE.  The keyframe is not indexed yet. */
+int orbmi_kfdb_store(orbmi_kfdb* db, int32_t kf_id, const uint32_t* word, const double* value, int n);
+/* KeyFrameDatabase::add (:40-46) / erase (:48-67) of a stored keyframe (unknown id: ORBMI_E_ARG).
+ * add gives the keyframe the next value of the handle's add counter: its position in every list
+ * of the reference's inverted file (add appends, erase keeps the others' order).  Adding an
+ * indexed keyframe returns ORBMI_E_STATE (the reference would list it twice); erasing one that is
+ * not indexed does nothing.  The stored vector stays after erase, for orbmi_kfdb_score. */
+int orbmi_kfdb_add(orbmi_kfdb* db, int32_t kf_id);
+int orbmi_kfdb_erase(orbmi_kfdb* db, int32_t kf_id);
+/* out_score[i] = mpVoc->score(query, mBowVec of kf_ids[i]) (L1Scoring / L2Scoring::score,
+ * Thirdparty/DBoW2/DBoW2/ScoringObject.cpp:23-120) in double, the reference's sum term by term in
+ * ascending word order: DetectLoop's minScore loop (src/LoopClosing.cc:126-140).  Any stored id,
+ * indexed or not; an unknown id returns ORBMI_E_ARG.  The query (nq <= 8192 words ascending) may
+ * be host or device memory, kf_ids and out_score are host memory. */
+int orbmi_kfdb_score(orbmi_kfdb* db, const uint32_t* q_word, const double* q_value, int nq, const int32_t* kf_ids,
+                     int n, double* out_score);
+
+/* One query's per-slot result (host arrays of max_keyframes entries each, any may be NULL). */
+typedef struct orbmi_kfdb_query_result {
+    int32_t n_slots;       /* out: slots in use                                                   */
+    int32_t max_common;    /* out: maxCommonWords (:113-118)                                      */
+    int32_t min_common;    /* out: (int)(maxCommonWords * 0.8f) (:120)                            */
+    int32_t* kf_id;        /* the slot's keyframe                                                 */
+    int32_t* common;       /* mnLoopWords; 0: not indexed, connected, or nothing shared           */
+    uint32_t* first_word;  /* the smallest shared word id (0xFFFFFFFF where common = 0)           */
+    uint64_t* add_seq;     /* the slot's add counter value                                        */
+    double* score;         /* mpVoc->score where common > min_common (:129-133), 0 elsewhere      */
+} orbmi_kfdb_query_result;
+
+/* The device part of KeyFrameDatabase::DetectLoopCandidates (:76-139) for the query vector of
+ * pKF: connected_ids = pKF->GetConnectedKeyFrames() (host memory; ids without a slot are
+ * ignored).  lKFsSharingWords is the slots with common > 0 in ascending (first_word, add_seq). */
+int orbmi_kfdb_query(orbmi_kfdb* db, const uint32_t* q_word, const double* q_value, int nq,
+                     const int32_t* connected_ids, int n_connected, orbmi_kfdb_query_result* out);
+
+/* KeyFrameDatabase::DetectLoopCandidates(pKF, minScore) (:76-197): the query above, then on the
+ * host the minScore filter, the accumulation over each survivor's GetBestCovisibilityKeyFrames(10)
+ * and the 0.75 * bestAccScore cut (:141-196).  The covisibility graph is the caller's:
+ * best_covis_ids[best_covis_off[k] .. best_covis_off[k + 1]) = GetBestCovisibilityKeyFrames(10)
+ * of keyframe id k in its order, for k < n_covis_kf (a keyframe past the table has none).
+ * out_ids (capacity out_capacity) receives vpLoopCandidates in the reference's order, *n_out
+ * their number; more than out_capacity returns ORBMI_E_CAP with *n_out = the number needed. */
+int orbmi_detect_loop_candidates(orbmi_kfdb* db, const uint32_t* q_word, const double* q_value, int nq,
+                                 float min_score, const int32_t* connected_ids, int n_connected,
+                                 const int32_t* best_covis_off, const int32_t* best_covis_ids, int n_covis_kf,
+                                 int32_t* out_ids, int out_capacity, int* n_out);
 
 /* ---- per-stage timing (HIP events on the handle's stream) ---------------------------- */
 

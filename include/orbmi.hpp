@@ -199,6 +199,21 @@ public:
         return n;
     }
 
+    // SearchByBoW(KeyFrame* pKF1, KeyFrame* pKF2, vector<MapPoint*>& vpMatches12)
+    // (src/ORBmatcher.cc:635-768): vpMatches12 as the KF2 keypoint index per KF1 keypoint, -1 none
+    int SearchByBoW(const orbmi_frame_view& KF1, const std::vector<uint8_t>& mapPointOk1,
+                    const orbmi_feature_vector& fv1, const orbmi_frame_view& KF2,
+                    const std::vector<uint8_t>& mapPointOk2, const orbmi_feature_vector& fv2,
+                    std::vector<int32_t>& match12) {
+        match12.assign(KF1.n > 0 ? KF1.n : 1, -1);
+        int n = 0;
+        check(orbmi_search_by_bow_kf(h_, &KF1, mapPointOk1.data(), &fv1, &KF2, mapPointOk2.data(), &fv2, mfNNratio,
+                                     mbCheckOrientation, match12.data(), &n),
+              "orbmi_search_by_bow_kf");
+        match12.resize(KF1.n);
+        return n;
+    }
+
     // SearchForTriangulation(KeyFrame*, KeyFrame*, cv::Mat F12, vector<pair<size_t,size_t>>&,
     // bool bOnlyStereo) (src/ORBmatcher.cc:783-975): the matched pairs in i1 order
     int SearchForTriangulation(const orbmi_frame_view& KF1, const std::vector<uint8_t>& hasMapPoint1,
@@ -316,6 +331,58 @@ public:
 
 private:
     orbmi_vocabulary* h_ = nullptr;
+};
+
+// ORB_SLAM2::KeyFrameDatabase (include/KeyFrameDatabase.h) on the device, by keyframe id
+// (pKF->mnId).  store() takes a keyframe's mBowVec once; add / erase are the reference's.  The
+// covisibility graph stays the caller's: DetectLoopCandidates takes pKF->GetConnectedKeyFrames()
+// as ids and GetBestCovisibilityKeyFrames(10) of every keyframe as a CSR indexed by id.
+class KeyFrameDatabase {
+public:
+    enum ScoringType { L1_NORM = 0, L2_NORM = 1 };
+    KeyFrameDatabase(int scoring, int maxKeyFrames, int maxWordsTotal, int device = 0) : cap_(maxKeyFrames) {
+        check(orbmi_kfdb_create(device, scoring, maxKeyFrames, maxWordsTotal, &h_), "orbmi_kfdb_create");
+    }
+    ~KeyFrameDatabase() { orbmi_kfdb_destroy(h_); }
+    KeyFrameDatabase(const KeyFrameDatabase&) = delete;
+    KeyFrameDatabase& operator=(const KeyFrameDatabase&) = delete;
+    orbmi_kfdb* handle() { return h_; }
+
+    void store(int32_t mnId, const ORBVocabulary::BowVector& v) {
+        check(orbmi_kfdb_store(h_, mnId, v.word.data(), v.value.data(), (int)v.word.size()), "orbmi_kfdb_store");
+    }
+    void add(int32_t mnId) { check(orbmi_kfdb_add(h_, mnId), "orbmi_kfdb_add"); }
+    void erase(int32_t mnId) { check(orbmi_kfdb_erase(h_, mnId), "orbmi_kfdb_erase"); }
+    void clear() { check(orbmi_kfdb_clear(h_), "orbmi_kfdb_clear"); }
+
+    // mpVoc->score(v, mBowVec of each id) (DetectLoop's minScore loop, src/LoopClosing.cc:126-140)
+    std::vector<double> score(const ORBVocabulary::BowVector& v, const std::vector<int32_t>& ids) {
+        std::vector<double> s(ids.size());
+        check(orbmi_kfdb_score(h_, v.word.data(), v.value.data(), (int)v.word.size(), ids.data(), (int)ids.size(),
+                               s.data()),
+              "orbmi_kfdb_score");
+        return s;
+    }
+
+    // DetectLoopCandidates(pKF, minScore) (src/KeyFrameDatabase.cc:76-197) -> vpLoopCandidates as ids
+    std::vector<int32_t> DetectLoopCandidates(const ORBVocabulary::BowVector& v, float minScore,
+                                              const std::vector<int32_t>& connected,
+                                              const std::vector<int32_t>& bestCovisOff,
+                                              const std::vector<int32_t>& bestCovisIds) {
+        std::vector<int32_t> out((size_t)cap_);
+        int n = 0;
+        check(orbmi_detect_loop_candidates(h_, v.word.data(), v.value.data(), (int)v.word.size(), minScore,
+                                           connected.data(), (int)connected.size(), bestCovisOff.data(),
+                                           bestCovisIds.data(), bestCovisOff.empty() ? 0 : (int)bestCovisOff.size() - 1,
+                                           out.data(), cap_, &n),
+              "orbmi_detect_loop_candidates");
+        out.resize((size_t)n);
+        return out;
+    }
+
+private:
+    orbmi_kfdb* h_ = nullptr;
+    int cap_;
 };
 
 // Optimizer::LocalBundleAdjustment (include/Optimizer.h:62) on the assembled local graph

@@ -5,9 +5,10 @@ for gfx950 behind a C ABI (include/orbmi.h, liborbmi.so).  This package holds th
 (csrc/), their build (build.py), the ctypes binding (_capi.py) and a Python mirror of the
 reference interface (orb.py) used by tests and bench.py.
 """
+from .loop import KeyFrameDatabase, LoopBackend, LoopDetector, detect_and_compute_sim3  # noqa: F401
 from .matcher import ORBmatcher  # noqa: F401
 from .orb import ORBextractor, compute_stereo_matches  # noqa: F401
 from .sim3 import Sim3Ransac, Sim3Solver, compute_sim3, solve_batch  # noqa: F401
 
-__all__ = ["ORBextractor", "ORBmatcher", "Sim3Ransac", "Sim3Solver", "compute_sim3", "compute_stereo_matches",
-           "solve_batch"]
+__all__ = ["KeyFrameDatabase", "LoopBackend", "LoopDetector", "ORBextractor", "ORBmatcher", "Sim3Ransac",
+           "Sim3Solver", "compute_sim3", "compute_stereo_matches", "detect_and_compute_sim3", "solve_batch"]

@@ -134,6 +134,16 @@ _PROTOS = {
     "orbmi_optimize_sim3_batch": (_i, [_vp, _i, _vp, _vp]),
     "orbmi_search_by_projection_sim3": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _f, C.POINTER(_i)]),
     "orbmi_debug_sim3_opt_linearize": (_i, [_vp, _vp, _vp, _vp, _vp]),
+    "orbmi_search_by_bow_kf": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _i, _vp, C.POINTER(_i)]),
+    "orbmi_kfdb_create": (_i, [_i, _i, _i, _i, C.POINTER(_vp)]),
+    "orbmi_kfdb_destroy": (None, [_vp]),
+    "orbmi_kfdb_clear": (_i, [_vp]),
+    "orbmi_kfdb_store": (_i, [_vp, C.c_int32, _vp, _vp, _i]),
+    "orbmi_kfdb_add": (_i, [_vp, C.c_int32]),
+    "orbmi_kfdb_erase": (_i, [_vp, C.c_int32]),
+    "orbmi_kfdb_score": (_i, [_vp, _vp, _vp, _i, _vp, _i, _vp]),
+    "orbmi_kfdb_query": (_i, [_vp, _vp, _vp, _i, _vp, _i, _vp]),
+    "orbmi_detect_loop_candidates": (_i, [_vp, _vp, _vp, _i, _f, _vp, _i, _vp, _vp, _i, _vp, _i, C.POINTER(_i)]),
     "orbmi_slam_create": (_i, [_vp, _i, _vp, C.POINTER(_vp)]),
     "orbmi_slam_destroy": (None, [_vp]),
     "orbmi_slam_wait_local_mapping": (_i, [_vp]),

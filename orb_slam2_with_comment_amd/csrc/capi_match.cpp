@@ -708,6 +708,37 @@ int orbmi_search_by_bow(orbmi_matcher* h, const orbmi_frame_view* kf, const uint
     return finish(m, outs, m.d_scalars, nmatches);
 }
 
+int orbmi_search_by_bow_kf(orbmi_matcher* h, const orbmi_frame_view* kf1, const uint8_t* ok1,
+                           const orbmi_feature_vector* fv1, const orbmi_frame_view* kf2, const uint8_t* ok2,
+                           const orbmi_feature_vector* fv2, float nnratio, int check_ori, int32_t* match12,
+                           int* nmatches) {
+    if (!h || !kf1 || !kf2 || !match12 || (kf1->n > 0 && !ok1) || (kf2->n > 0 && !ok2)) return ORBMI_E_ARG;
+    if (kf1->n_device || kf2->n_device) return ORBMI_E_ARG;  // keyframes: host-known counts
+    Matcher& m = h->m;
+    ORBMI_HIP(hipSetDevice(m.device));
+    m.arena_reset();
+    DevFrame K1, K2;
+    DevFV f1, f2;
+    int rc;
+    if ((rc = make_frame(m, kf1, &K1, false))) return rc;
+    if ((rc = make_frame(m, kf2, &K2, false))) return rc;
+    if ((rc = make_fv(m, fv1, &f1))) return rc;
+    if ((rc = make_fv(m, fv2, &f2))) return rc;
+    const uint8_t* d_ok1 = dev_in(m, ok1, (size_t)K1.n, &rc);
+    const uint8_t* d_ok2 = dev_in(m, ok2, (size_t)K2.n, &rc);
+    if (rc) return rc;
+    if ((rc = scalars(m))) return rc;
+    int* d_matched2 = (int*)m.stage((size_t)std::max(K2.n, 1) * sizeof(int));  // vbMatched2
+    if (!d_matched2) return ORBMI_E_HIP;
+    std::vector<OutBuf> outs;
+    int* d_out = dev_out(m, match12, (size_t)K1.n, outs);
+    if ((rc = orbmi::launch_bow_kf(m, K1, d_ok1, f1, K2, d_ok2, f2, nnratio, check_ori, d_out, d_matched2,
+                                   m.d_scalars)))
+        return rc;
+    ORBMI_HIP(hipGetLastError());
+    return finish(m, outs, m.d_scalars, nmatches);
+}
+
 int orbmi_match_descriptors_segments(orbmi_matcher* h, const uint8_t* q_desc, int nq, const int* nq_device,
                                      const uint8_t* train_desc, int nseg, int seg_capacity, const int* seg_counts,
                                      int skip_seg, int th, float ratio, int32_t* match, int* nmatches) {

@@ -200,6 +200,9 @@ int launch_track_update(Matcher& m, const DevFrame& F, int stage, const uint8_t*
                         int n_mp, uint8_t* occ_out, int* counts);
 int launch_bow(Matcher& m, const DevFrame& KF, const uint8_t* kf_ok, const DevFV& kfv, const DevFrame& F,
                const DevFV& fv, float nnratio, int check_ori, int* match, int* nmatches);
+int launch_bow_kf(Matcher& m, const DevFrame& KF1, const uint8_t* ok1, const DevFV& fv1, const DevFrame& KF2,
+                  const uint8_t* ok2, const DevFV& fv2, float nnratio, int check_ori, int* match12, int* matched2,
+                  int* nmatches);
 int launch_triangulation(Matcher& m, const DevFrame& KF1, const uint8_t* has_mp1, const DevFV& fv1, int npairs,
                          TriPair* pairs_host, TriPair* pairs_dev, int only_stereo, int check_ori, int* match);
 namespace tri { struct Side; }

@@ -1055,6 +1055,77 @@ __global__ __launch_bounds__(256) void k_bow_match(DevFrame KF, const uint8_t* _
     }
 }
 
+// SearchByBoW(KeyFrame*, KeyFrame*, vpMatches12) (src/ORBmatcher.cc:635-768), the sibling of
+// k_bow_match: one wave per KF1 node.  What differs from the (KF, Frame) form: both sides need a
+// live map point (ok1 gates the outer loop :671-675, ok2 the inner one beside vbMatched2
+// :687-693), acceptance is the strict bestDist1 < TH_LOW (:711), the output is indexed by KF1's
+// keypoint (match12[idx1] = idx2), rot = angle1 - angle2 and the histogram holds idx1.
+// vbMatched2 lives in `matched2` (one int per KF2 keypoint, zeroed by the launcher) and, for the
+// first 64 * kPer features of the node, in registers; features past that window re-read it.
+__global__ __launch_bounds__(256) void k_bow_match_kf(DevFrame KF1, const uint8_t* __restrict__ ok1, DevFV fv1,
+                                                      DevFrame KF2, const uint8_t* __restrict__ ok2, DevFV fv2,
+                                                      float nnratio, int check_ori, int* __restrict__ match12,
+                                                      int* __restrict__ matched2, int* __restrict__ bin_of,
+                                                      int* __restrict__ hist) {
+    const int wid = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int a = blockIdx.x * 4 + wid;
+    if (a >= fv1.nnodes) return;
+    const unsigned id = fv1.node_id[a];
+    int lo = 0, hi = fv2.nnodes;  // lower_bound
+    while (lo < hi) { const int mid = (lo + hi) >> 1; if (fv2.node_id[mid] < id) lo = mid + 1; else hi = mid; }
+    if (lo >= fv2.nnodes || fv2.node_id[lo] != id) return;
+    const int f0 = fv2.off[lo], nf = fv2.off[lo + 1] - f0;
+    constexpr int kPer = 8;  // KF2 features per lane kept in registers
+    bool matched[kPer];
+#pragma unroll
+    for (int k = 0; k < kPer; k++) matched[k] = false;
+    for (int ia = fv1.off[a]; ia < fv1.off[a + 1]; ia++) {
+        const int idx1 = fv1.feat[ia];
+        if ((unsigned)idx1 >= (unsigned)KF1.n || !ok1[idx1]) continue;
+        const uint8_t* d1 = KF1.desc + 32 * (long long)idx1;
+        unsigned long long b1 = ~0ull, b2 = ~0ull;
+        for (int base = 0; base < nf; base += 64 * kPer) {
+#pragma unroll
+            for (int k = 0; k < kPer; k++) {
+                const int pos = base + k * 64 + lane;
+                if (pos >= nf) continue;
+                const int idx2 = fv2.feat[f0 + pos];
+                if ((unsigned)idx2 >= (unsigned)KF2.n || !ok2[idx2]) continue;
+                const bool done = base == 0 ? matched[k] : matched2[idx2] != 0;
+                if (done) continue;
+                const unsigned long long e = ((unsigned long long)popc_desc(d1, KF2.desc + 32 * (long long)idx2) << 32) | (unsigned)pos;
+                if (e < b1) { b2 = b1; b1 = e; } else if (e < b2) b2 = e;
+            }
+        }
+        // (dist, position) keys: the least one is the first feature in node order at bestDist1
+        const unsigned long long m1 = wave_min_u64(b1);
+        const unsigned long long c2 = b1 == m1 ? b2 : b1;
+        const unsigned long long m2 = wave_min_u64(c2);
+        const int bestDist1 = m1 == ~0ull ? 256 : (int)(m1 >> 32);
+        const int bestDist2 = m2 == ~0ull ? 256 : (int)(m2 >> 32);
+        if (bestDist1 < TH_LOW && (float)bestDist1 < nnratio * (float)bestDist2) {
+            const int pos = (int)(m1 & 0xFFFFFFFFu);
+            const int idx2 = fv2.feat[f0 + pos];
+            if (pos < 64 * kPer && lane == (pos & 63)) {
+#pragma unroll
+                for (int k = 0; k < kPer; k++)
+                    if (k == (pos >> 6)) matched[k] = true;
+            }
+            if (lane == 0) {
+                match12[idx1] = idx2;
+                matched2[idx2] = 1;
+                if (check_ori) {
+                    const int bin = rot_bin(KF1.keys[idx1].angle, KF2.keys[idx2].angle);
+                    bin_of[idx1] = bin;
+                    atomicAdd(&hist[bin], 1);
+                }
+            }
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+        }
+    }
+}
+
 // rotation-histogram filter (ComputeThreeMaxima, src/ORBmatcher.cc:1854-1895) of one search's
 // matches and their count, one workgroup
 __device__ inline void finalize_block(int n, int check_ori, const int* __restrict__ hist,
@@ -1352,6 +1423,23 @@ int launch_bow(Matcher& m, const DevFrame& KF, const uint8_t* kf_ok, const DevFV
         hipLaunchKernelGGL(k_bow_match, dim3((kfv.nnodes + 3) / 4), dim3(256), 0, m.ls(), KF, kf_ok, kfv, F, fv,
                            nnratio, check_ori, match, m.d_bin_of, m.d_hist);
     hipLaunchKernelGGL(k_bow_finalize, dim3(1), dim3(1024), 0, m.ls(), F, check_ori, m.d_hist, m.d_bin_of, match,
+                       nmatches);
+    return ORBMI_OK;
+}
+
+int launch_bow_kf(Matcher& m, const DevFrame& KF1, const uint8_t* ok1, const DevFV& fv1, const DevFrame& KF2,
+                  const uint8_t* ok2, const DevFV& fv2, float nnratio, int check_ori, int* match12, int* matched2,
+                  int* nmatches) {
+    int rc;
+    if ((rc = ensure_buf(&m.d_bin_of, &m.cap_bin_of, (size_t)std::max(KF1.n, 1)))) return rc;
+    if ((rc = ensure_buf(&m.d_hist, &m.cap_hist, (size_t)HISTO_LENGTH))) return rc;
+    ORBMI_HIP(hipMemsetAsync(m.d_hist, 0, HISTO_LENGTH * sizeof(int), m.ls()));
+    ORBMI_HIP(hipMemsetAsync(match12, 0xFF, (size_t)std::max(KF1.n, 1) * sizeof(int), m.ls()));
+    ORBMI_HIP(hipMemsetAsync(matched2, 0, (size_t)std::max(KF2.n, 1) * sizeof(int), m.ls()));
+    if (fv1.nnodes > 0 && fv2.nnodes > 0)
+        hipLaunchKernelGGL(k_bow_match_kf, dim3((fv1.nnodes + 3) / 4), dim3(256), 0, m.ls(), KF1, ok1, fv1, KF2, ok2,
+                           fv2, nnratio, check_ori, match12, matched2, m.d_bin_of, m.d_hist);
+    hipLaunchKernelGGL(k_bow_finalize, dim3(1), dim3(1024), 0, m.ls(), KF1, check_ori, m.d_hist, m.d_bin_of, match12,
                        nmatches);
     return ORBMI_OK;
 }

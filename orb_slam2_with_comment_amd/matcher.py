@@ -182,3 +182,22 @@ class ORBmatcher:
                                         C.addressof(ff), self.mfNNratio, int(self.mbCheckOrientation),
                                         out.ctypes.data, C.byref(n)))
         return out[:len(f.keys)], n.value
+
+    def SearchByBoWKF(self, kf1, ok1, fv1, kf2, ok2, fv2, nnratio=None, checkOri=None):
+        """SearchByBoW(KeyFrame*, KeyFrame*, vector<MapPoint*>& vpMatches12)
+        (src/ORBmatcher.cc:635-768): ok = the slot holds a map point that is not bad, fv = mFeatVec.
+        Returns (match12, nmatches): match12[i1] = the KF2 keypoint matched to KF1 keypoint i1, -1
+        for none -- the bow_matches row compute_sim3 takes.  nnratio / checkOri override the
+        matcher's own (ComputeSim3 builds an ORBmatcher(0.75, true) for this call)."""
+        n1, n2 = len(kf1.keys), len(kf2.keys)
+        o1, o2 = np.ascontiguousarray(ok1, np.uint8), np.ascontiguousarray(ok2, np.uint8)
+        if len(o1) != n1 or len(o2) != n2:
+            raise ValueError("SearchByBoWKF takes one flag per keypoint slot")
+        out = np.zeros(max(n1, 1), np.int32)
+        n = C.c_int()
+        v1, v2, f1, f2 = kf1.view(), kf2.view(), fv1.view(), fv2.view()
+        check("orbmi_search_by_bow_kf", lib().orbmi_search_by_bow_kf(
+            self._h, C.addressof(v1), o1.ctypes.data if n1 else None, C.addressof(f1), C.addressof(v2),
+            o2.ctypes.data if n2 else None, C.addressof(f2), self.mfNNratio if nnratio is None else nnratio,
+            int(self.mbCheckOrientation if checkOri is None else checkOri), out.ctypes.data, C.byref(n)))
+        return out[:n1], n.value
