@@ -1083,6 +1083,106 @@ int orbmi_detect_loop_candidates(orbmi_kfdb* db, const uint32_t* q_word, const d
                                  const int32_t* best_covis_off, const int32_t* best_covis_ids, int n_covis_kf,
                                  int32_t* out_ids, int out_capacity, int* n_out);
 
+/* ---- LoopClosing::CorrectLoop: Optimizer::OptimizeEssentialGraph --------------------- */
+
+/* A Sim3 here is 8 doubles: the rotation q (x y z w, Eigen's coefficient order), t, s. */
+
+/* The graph OptimizeEssentialGraph reads, as host arrays indexed by keyframe id (n_ids =
+ * nMaxKFid + 1; ids may have gaps: live[id] = 0).  Tcw: 4x4 row-major float per id; parent: the
+ * spanning-tree parent or -1; loop_* / cov_* / lc_*: GetLoopEdges, GetCovisiblesByWeight(100) (in
+ * that function's order) and LoopConnections as CSR over the ids (off has n_ids + 1 entries),
+ * lc_weight the GetWeight of each listed pair; corrected / noncorrected: the CorrectedSim3 and
+ * NonCorrectedSim3 maps as (id, Sim3) lists; loop_id / cur_id: pLoopKF and pCurKF. */
+typedef struct orbmi_essgraph_input {
+    int32_t n_ids;
+    const uint8_t* live;
+    const float* Tcw;
+    const int32_t* parent;
+    const int32_t* loop_off;
+    const int32_t* loop_ids;
+    const int32_t* cov_off;
+    const int32_t* cov_ids;
+    int32_t n_corrected;
+    const int32_t* corrected_ids;
+    const double* corrected;
+    int32_t n_noncorrected;
+    const int32_t* noncorrected_ids;
+    const double* noncorrected;
+    const int32_t* lc_off;
+    const int32_t* lc_ids;
+    const int32_t* lc_weight;
+    int32_t loop_id, cur_id;
+} orbmi_essgraph_input;
+
+/* The edge list of OptimizeEssentialGraph (src/Optimizer.cc:862-1053), on the host: vScw (n_ids x
+ * 8; the identity where no keyframe lives) = the corrected Sim3 where there is one, else
+ * Sim3(Rcw, tcw, 1); then the LoopConnections edges ((i, j) skipped when (i != cur || j != loop)
+ * and weight < 100, every listed direction its own edge), then per keyframe the parent edge, the
+ * loop edges to a smaller id, and the covisibility edges to a smaller id that is not the parent,
+ * a child, a loop-edge partner or a pair the LoopConnections inserted.  v0 = i, v1 = j (keyframe
+ * ids), measurement = Sjw * Swi with NonCorrectedSim3 taking precedence on the normal edges.
+ * Wherever the reference iterates a container keyed by KeyFrame* the order here is ascending
+ * keyframe id.  At most n_live + the three CSR lengths edges; more than max_edges returns
+ * ORBMI_E_CAP with *n_edges = the number needed.  ORBMI_E_ARG: a NULL array, an id out of range
+ * or naming a keyframe that does not live, offsets that do not ascend. */
+int orbmi_essential_graph_edges(const orbmi_essgraph_input* graph, int max_edges, int32_t* v0, int32_t* v1,
+                                double* measurements, double* vScw, int* n_edges);
+
+/* One pose graph: n_vertices VertexSim3Expmap (vertices: n_vertices x 8, the initial estimates),
+ * vertex `fixed` held, n_edges EdgeSim3 with identity information between vertices v0[e] and
+ * v1[e] (indices into `vertices`), measurements n_edges x 8.  iterations <= 32 (the reference:
+ * 20).  profile != 0 brackets the phases with HIP events (and waits for each). */
+typedef struct orbmi_essgraph_problem {
+    int32_t n_vertices;
+    const double* vertices;
+    int32_t fixed;
+    int32_t n_edges;
+    const int32_t* v0;
+    const int32_t* v1;
+    const double* measurements;
+    int32_t fix_scale;
+    int32_t iterations;
+    int32_t profile;
+} orbmi_essgraph_problem;
+
+#define ORBMI_EG_TERMINATE 1    /* Levenberg stopped by a rule of its own (else: ran to the count) */
+#define ORBMI_EG_SOLVE_FAILED 2 /* a damped solve met a pivot that is not a positive finite number */
+#define ORBMI_EG_REJECTED 4     /* a trial was rejected and the estimates restored                 */
+
+/* vertices (n_vertices x 8, host memory): the optimised estimates; chi2 before the first and after
+ * the last accepted step; iterations = outer Levenberg iterations, trials[k] the solves of
+ * iteration k; status = ORBMI_EG_* or'ed; phase_ms: linearisation, assembly, factor + solve,
+ * update, summed over the call (profile only). */
+typedef struct orbmi_essgraph_result {
+    double* vertices;
+    double chi2_before, chi2_after;
+    int32_t iterations;
+    int32_t status;
+    int32_t trials[32];
+    float phase_ms[4];
+} orbmi_essgraph_result;
+
+/* optimizer.optimize(iterations) of OptimizeEssentialGraph (src/Optimizer.cc:1055-1057) on the
+ * matcher handle's stream: numeric Jacobians as BaseBinaryEdge::linearizeOplus computes them, H
+ * and b gathered in edge order, OptimizationAlgorithmLevenberg::solve with setUserLambdaInit(1e-16)
+ * and a block-sparse LDL^T in a minimum-degree order; the Levenberg decisions are taken on the
+ * host from one small read-back per trial.  A vertex no edge names is returned as given, and a
+ * graph with nothing to optimise returns 0 iterations with ORBMI_EG_TERMINATE.  Every loop is
+ * bounded by the reference's counts, so non-finite input terminates too (its status carries
+ * ORBMI_EG_SOLVE_FAILED).  ORBMI_E_ARG before anything is launched: a NULL array, n_vertices < 1,
+ * `fixed` or an edge's vertex out of range, v0 == v1, iterations outside [0, 32]. */
+int orbmi_optimize_essential_graph(orbmi_matcher* m, const orbmi_essgraph_problem* problem, orbmi_essgraph_result* result);
+
+/* The two arithmetic loops of CorrectLoop (src/LoopClosing.cc:607-628) and the tail of
+ * OptimizeEssentialGraph (src/Optimizer.cc:1069-1114): out_points[i] (float) =
+ * Swr_corrected[ref[i]].map(Srw[ref[i]].map((double)points[i])), ref[i] in [0, n_ref) naming the
+ * point's reference keyframe in the two Sim3 tables (n_ref x 8 each); out_tcw[k] (4x4 row-major
+ * float) = [R | t * (1. / s)] of poses[k] (n_poses x 8).  Host arrays.  UpdateNormalAndDepth stays
+ * the caller's.  ORBMI_E_ARG before the launch: a NULL array, a ref outside the tables. */
+int orbmi_correct_points_sim3(orbmi_matcher* m, int n_points, const float* points, const int32_t* ref, int n_ref,
+                              const double* Srw, const double* Swr_corrected, float* out_points, int n_poses,
+                              const double* poses, float* out_tcw);
+
 /* ---- per-stage timing (HIP events on the handle's stream) ---------------------------- */
 
 /* Kernel stages of one handle; each is a single kernel launch (resize: one per level). */

@@ -619,6 +619,75 @@ inline int OptimizeSim3(ORBmatcher& matcher, const Sim3OptInput& in, Sim3OptOutp
     return out.nIn;
 }
 
+// Optimizer::OptimizeEssentialGraph (src/Optimizer.cc:829-1118) over plain vectors: the pose graph
+// as the reference builds it (orbmi_essential_graph_edges gives the edges from the map's arrays).
+// A Sim3 is 8 doubles: q (x y z w), t, s.
+struct EssentialGraphInput {
+    std::vector<double> vertices;       // n x 8: vScw of every live keyframe
+    int fixed = 0;                      // index of pLoopKF among them
+    std::vector<int32_t> v0, v1;        // per edge: indices into vertices
+    std::vector<double> measurements;   // per edge x 8: Sji
+    bool bFixScale = true;
+    int iterations = 20;
+};
+
+struct EssentialGraphOutput {
+    std::vector<double> vertices;       // n x 8: the optimised Sim3s
+    std::vector<float> Tcw;             // n x 16: [R | t / s], what pKFi->SetPose takes
+    double chi2Before = 0, chi2After = 0;
+    int iterations = 0, status = 0;     // status: ORBMI_EG_* or'ed
+    std::vector<int> trials;            // per iteration
+};
+
+struct Optimizer {
+    // void Optimizer::OptimizeEssentialGraph(pMap, pLoopKF, pCurKF, NonCorrectedSim3, CorrectedSim3,
+    // LoopConnections, bFixScale), from the edge list on: optimize(20) and the SE3 pose recovery
+    static EssentialGraphOutput OptimizeEssentialGraph(ORBmatcher& matcher, const EssentialGraphInput& in) {
+        const size_t n = in.vertices.size() / 8, ne = in.v0.size();
+        if (in.vertices.size() != 8 * n || n == 0 || in.v1.size() != ne || in.measurements.size() != 8 * ne)
+            throw Error(ORBMI_E_ARG, "OptimizeEssentialGraph");
+        orbmi_essgraph_problem p{};
+        p.n_vertices = (int32_t)n;
+        p.vertices = in.vertices.data();
+        p.fixed = in.fixed;
+        p.n_edges = (int32_t)ne;
+        p.v0 = in.v0.data();
+        p.v1 = in.v1.data();
+        p.measurements = in.measurements.data();
+        p.fix_scale = in.bFixScale;
+        p.iterations = in.iterations;
+        EssentialGraphOutput out;
+        out.vertices.assign(8 * n, 0.0);
+        out.Tcw.assign(16 * n, 0.0f);
+        orbmi_essgraph_result r{};
+        r.vertices = out.vertices.data();
+        check(orbmi_optimize_essential_graph(matcher.handle(), &p, &r), "orbmi_optimize_essential_graph");
+        check(orbmi_correct_points_sim3(matcher.handle(), 0, nullptr, nullptr, 0, nullptr, nullptr, nullptr, (int)n,
+                                        out.vertices.data(), out.Tcw.data()),
+              "orbmi_correct_points_sim3");
+        out.chi2Before = r.chi2_before;
+        out.chi2After = r.chi2_after;
+        out.iterations = r.iterations;
+        out.status = r.status;
+        out.trials.assign(r.trials, r.trials + r.iterations);
+        return out;
+    }
+
+    // The map-point loop of CorrectLoop / OptimizeEssentialGraph (src/LoopClosing.cc:607-612,
+    // src/Optimizer.cc:1105-1114): points n x 3, ref[i] indexes the two Sim3 tables (m x 8 each)
+    static std::vector<float> CorrectPoints(ORBmatcher& matcher, const std::vector<float>& points, const std::vector<int32_t>& ref,
+                                            const std::vector<double>& Srw, const std::vector<double>& correctedSwr) {
+        const size_t n = ref.size();
+        if (points.size() != 3 * n || Srw.size() != correctedSwr.size() || Srw.size() % 8) throw Error(ORBMI_E_ARG, "CorrectPoints");
+        std::vector<float> out(3 * n ? 3 * n : 1);
+        check(orbmi_correct_points_sim3(matcher.handle(), (int)n, points.data(), ref.data(), (int)(Srw.size() / 8), Srw.data(),
+                                        correctedSwr.data(), out.data(), 0, nullptr, nullptr),
+              "orbmi_correct_points_sim3");
+        out.resize(3 * n);
+        return out;
+    }
+};
+
 // ORB_SLAM2::System for the RGB-D sensor (include/System.h:58-83, src/System.cc:161-210) over the
 // native loop (orbmi_slam_create_rgbd / orbmi_slam_track_rgbd).  settings: the Tracking
 // constructor's reads (src/Tracking.cc:53-143); rgbd: mDistCoef, mDepthMapFactor (already

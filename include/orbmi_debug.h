@@ -140,6 +140,17 @@ int orbmi_slam_get_phase_ms(orbmi_slam* h, double* ms, int n, long* frames);
 int orbmi_debug_sim3_opt_linearize(orbmi_matcher* m, const orbmi_sim3_opt_problem* problem, double* H, double* b,
                                    double* chi2);
 
+/* One buildSystem pass of orbmi_optimize_essential_graph at the problem's initial estimates, in the
+ * library's block storage: dims[0] = nf free vertices (not fixed, named by an edge), dims[1] = nl
+ * off-diagonal blocks of L; vert_of (nf): the vertex of every rank of the elimination order;
+ * col_ptr (nf + 1) / row_of (nl): the blocks of column c are rows row_of[col_ptr[c] ..
+ * col_ptr[c + 1]) (ranks, ascending); Hd (nf x 49) / Ho (nl x 49): H before damping, row-major
+ * blocks (row = the later rank), fill blocks 0; b (nf x 7); chi2 (1).  With vert_of NULL only dims
+ * is written, to size the arrays. */
+int orbmi_debug_essgraph_linearize(orbmi_matcher* m, const orbmi_essgraph_problem* problem, int32_t* dims,
+                                   int32_t* vert_of, int32_t* col_ptr, int32_t* row_of, double* Hd, double* Ho,
+                                   double* b, double* chi2);
+
 #ifdef __cplusplus
 }
 #endif

@@ -144,6 +144,10 @@ _PROTOS = {
     "orbmi_kfdb_score": (_i, [_vp, _vp, _vp, _i, _vp, _i, _vp]),
     "orbmi_kfdb_query": (_i, [_vp, _vp, _vp, _i, _vp, _i, _vp]),
     "orbmi_detect_loop_candidates": (_i, [_vp, _vp, _vp, _i, _f, _vp, _i, _vp, _vp, _i, _vp, _i, C.POINTER(_i)]),
+    "orbmi_essential_graph_edges": (_i, [_vp, _i, _vp, _vp, _vp, _vp, C.POINTER(_i)]),
+    "orbmi_optimize_essential_graph": (_i, [_vp, _vp, _vp]),
+    "orbmi_correct_points_sim3": (_i, [_vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp]),
+    "orbmi_debug_essgraph_linearize": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "orbmi_slam_create": (_i, [_vp, _i, _vp, C.POINTER(_vp)]),
     "orbmi_slam_destroy": (None, [_vp]),
     "orbmi_slam_wait_local_mapping": (_i, [_vp]),

@@ -5,6 +5,8 @@
 #include <new>
 
 #include "matcher.h"
+#include "essgraph_edges.h"
+#include "essgraph_launch.h"
 #include "sim3.h"
 #include "sim3_horn.h"
 #include "tri_geom.h"
@@ -1404,6 +1406,280 @@ int orbmi_debug_sim3_opt_linearize(orbmi_matcher* h, const orbmi_sim3_opt_proble
     memcpy(b, lin + 49, 7 * sizeof(double));
     *chi2 = lin[56];
     return ORBMI_OK;
+}
+
+}  // extern "C"
+
+namespace {
+
+static_assert(sizeof(orbmi::Sim3d) == 8 * sizeof(double), "a Sim3 is 8 doubles in the C interface");
+
+bool essgraph_args_ok(const orbmi_essgraph_problem& P) {
+    if (P.n_vertices < 1 || !P.vertices || P.n_edges < 0 || P.iterations < 0 || P.iterations > 32) return false;
+    if (P.fixed < 0 || P.fixed >= P.n_vertices) return false;
+    return P.n_edges == 0 || (P.v0 && P.v1 && P.measurements);
+}
+
+std::vector<orbmi::EgEdge> essgraph_edges_of(const orbmi_essgraph_problem& P) {
+    std::vector<orbmi::EgEdge> E((size_t)P.n_edges);
+    for (int e = 0; e < P.n_edges; e++) {
+        E[e].v0 = P.v0[e];
+        E[e].v1 = P.v1[e];
+        memcpy(&E[e].C, P.measurements + 8 * (size_t)e, sizeof(orbmi::Sim3d));
+    }
+    return E;
+}
+
+template <class T>
+T* essgraph_put(Matcher& m, const std::vector<T>& v, int* rc) {
+    T* d = (T*)m.stage(std::max(v.size(), (size_t)1) * sizeof(T));
+    if (!d || m.h2d(d, v.data(), v.size() * sizeof(T)) != hipSuccess) *rc = ORBMI_E_HIP;
+    return d;
+}
+
+// One call's device state: the plan's tables, the edges and two copies of the estimates
+struct EssgraphCall {
+    orbmi::EgPlan plan;
+    orbmi::EgDev D;
+    orbmi::Sim3d *est = nullptr, *trial = nullptr;
+};
+
+int essgraph_stage(Matcher& m, const orbmi_essgraph_problem& P, const std::vector<orbmi::EgEdge>& E, EssgraphCall* C) {
+    C->plan = orbmi::eg_plan(P.n_vertices, P.fixed, P.n_edges, E.data());
+    const orbmi::EgPlan& Q = C->plan;
+    if (!orbmi::eg_plan_ok(Q)) return ORBMI_E_ARG;  // every table index against its array, before any launch
+    int rc = 0;
+    orbmi::EgDev& D = C->D;
+    memset(&D, 0, sizeof(D));
+    D.nv = Q.nv; D.ne = Q.ne; D.nf = Q.nf; D.nl = Q.nl;
+    D.fix_scale = P.fix_scale != 0;
+    D.edges = essgraph_put(m, E, &rc);
+    D.vert_of = essgraph_put(m, Q.vert_of, &rc);
+    D.col_ptr = essgraph_put(m, Q.col_ptr, &rc);
+    D.row_of = essgraph_put(m, Q.row_of, &rc);
+    D.upd_ptr = essgraph_put(m, Q.upd_ptr, &rc);
+    D.upd = essgraph_put(m, Q.upd, &rc);
+    D.asm_ptr = essgraph_put(m, Q.asm_ptr, &rc);
+    D.asm_ent = essgraph_put(m, Q.asm_ent, &rc);
+    auto doubles = [&](size_t n) { return (double*)m.stage(std::max(n, (size_t)1) * sizeof(double)); };
+    D.recs = doubles((size_t)Q.ne * orbmi::kEgRec);
+    D.Hd = doubles((size_t)Q.nf * 49); D.Ho = doubles((size_t)Q.nl * 49); D.b = doubles((size_t)Q.nf * 7);
+    D.Ld = doubles((size_t)Q.nf * 49); D.Lo = doubles((size_t)Q.nl * 49); D.x = doubles((size_t)Q.nf * 7);
+    D.y = doubles((size_t)Q.nf * 7);
+    D.chi2 = doubles((size_t)Q.ne);
+    D.out = doubles(orbmi::kEgOut);
+    const size_t vb = (size_t)P.n_vertices * sizeof(orbmi::Sim3d);
+    C->est = (orbmi::Sim3d*)m.stage(vb);
+    C->trial = (orbmi::Sim3d*)m.stage(vb);
+    if (rc || !D.recs || !D.Hd || !D.Ho || !D.b || !D.Ld || !D.Lo || !D.x || !D.y || !D.chi2 || !D.out || !C->est || !C->trial)
+        return ORBMI_E_HIP;
+    if (m.h2d(C->est, P.vertices, vb) != hipSuccess || m.h2d(C->trial, P.vertices, vb) != hipSuccess) return ORBMI_E_HIP;
+    ORBMI_HIP(m.flush_up());
+    if (m.up_err != hipSuccess) return ORBMI_E_HIP;
+    // fill blocks are never written by the assembly
+    if (Q.nl) ORBMI_HIP(hipMemsetAsync(D.Ho, 0, (size_t)Q.nl * 49 * sizeof(double), m.ls()));
+    return ORBMI_OK;
+}
+
+// HIP events around one phase of a profiled call
+struct EssgraphTimer {
+    Matcher& m;
+    bool on;
+    hipEvent_t a = nullptr, b = nullptr;
+    EssgraphTimer(Matcher& m_, bool on_) : m(m_), on(on_) {
+        if (on && (hipEventCreate(&a) != hipSuccess || hipEventCreate(&b) != hipSuccess)) on = false;
+    }
+    ~EssgraphTimer() {
+        if (a) (void)hipEventDestroy(a);
+        if (b) (void)hipEventDestroy(b);
+    }
+    void begin() { if (on) (void)hipEventRecord(a, m.ls()); }
+    void end(float* acc) {
+        if (!on) return;
+        float ms = 0;
+        if (hipEventRecord(b, m.ls()) == hipSuccess && hipEventSynchronize(b) == hipSuccess &&
+            hipEventElapsedTime(&ms, a, b) == hipSuccess)
+            *acc += ms;
+    }
+};
+
+}  // namespace
+
+extern "C" {
+
+int orbmi_essential_graph_edges(const orbmi_essgraph_input* g, int max_edges, int32_t* v0, int32_t* v1,
+                                double* measurements, double* vScw, int* n_edges) {
+    if (!g || !n_edges || !vScw || max_edges < 0 || (max_edges > 0 && (!v0 || !v1 || !measurements))) return ORBMI_E_ARG;
+    orbmi::EgGraphIn G;
+    G.n_ids = g->n_ids;
+    G.live = g->live; G.Tcw = g->Tcw; G.parent = g->parent;
+    G.loop_off = g->loop_off; G.loop_ids = g->loop_ids;
+    G.cov_off = g->cov_off; G.cov_ids = g->cov_ids;
+    G.n_corrected = g->n_corrected; G.corrected_ids = g->corrected_ids; G.corrected = (const orbmi::Sim3d*)g->corrected;
+    G.n_noncorrected = g->n_noncorrected; G.noncorrected_ids = g->noncorrected_ids;
+    G.noncorrected = (const orbmi::Sim3d*)g->noncorrected;
+    G.lc_off = g->lc_off; G.lc_ids = g->lc_ids; G.lc_weight = g->lc_weight;
+    G.loop_id = g->loop_id; G.cur_id = g->cur_id;
+    if (!orbmi::eg_graph_args_ok(G)) return ORBMI_E_ARG;
+    std::vector<orbmi::EgGraphEdge> E;
+    std::vector<orbmi::Sim3d> S;
+    orbmi::eg_graph_edges(G, &E, &S);
+    memcpy(vScw, S.data(), S.size() * sizeof(orbmi::Sim3d));
+    *n_edges = (int)E.size();
+    if ((int)E.size() > max_edges) return ORBMI_E_CAP;
+    for (size_t e = 0; e < E.size(); e++) {
+        v0[e] = E[e].v0;
+        v1[e] = E[e].v1;
+        memcpy(measurements + 8 * e, &E[e].S, sizeof(orbmi::Sim3d));
+    }
+    return ORBMI_OK;
+}
+
+int orbmi_optimize_essential_graph(orbmi_matcher* h, const orbmi_essgraph_problem* problem, orbmi_essgraph_result* result) {
+    if (!h || !problem || !result || !result->vertices || !essgraph_args_ok(*problem)) return ORBMI_E_ARG;
+    const orbmi_essgraph_problem& P = *problem;
+    const std::vector<orbmi::EgEdge> E = essgraph_edges_of(P);
+    if (!orbmi::eg_args_ok(P.n_vertices, P.fixed, P.n_edges, E.data())) return ORBMI_E_ARG;
+    orbmi_essgraph_result& R = *result;
+    R.chi2_before = R.chi2_after = 0;
+    R.iterations = 0;
+    R.status = 0;
+    memset(R.trials, 0, sizeof(R.trials));
+    memset(R.phase_ms, 0, sizeof(R.phase_ms));
+    const size_t vb = (size_t)P.n_vertices * sizeof(orbmi::Sim3d);
+    Matcher& m = h->m;
+    ORBMI_HIP(hipSetDevice(m.device));
+    m.arena_reset();
+    EssgraphCall C;
+    int rc = essgraph_stage(m, P, E, &C);
+    if (rc) return rc;
+    if (C.plan.nf == 0 || P.n_edges == 0 || P.iterations == 0) {  // nothing to optimise
+        memmove(R.vertices, P.vertices, vb);
+        R.status = ORBMI_EG_TERMINATE;
+        ORBMI_HIP(hipStreamSynchronize(m.ls()));
+        return ORBMI_OK;
+    }
+    const orbmi::EgDev& D = C.D;
+    EssgraphTimer T(m, P.profile != 0);
+    orbmi::S3oLm L{};
+    double out[orbmi::kEgOut];
+    auto read_out = [&]() -> int {
+        ORBMI_HIP(hipMemcpyAsync(out, D.out, sizeof(out), hipMemcpyDeviceToHost, m.ls()));
+        ORBMI_HIP(hipStreamSynchronize(m.ls()));
+        return ORBMI_OK;
+    };
+    bool stopped = false;
+    for (int it = 0; it < P.iterations; it++) {
+        T.begin();
+        if ((rc = orbmi::launch_eg_linearize(m, D, C.est))) return rc;
+        T.end(&R.phase_ms[0]);
+        T.begin();
+        if ((rc = orbmi::launch_eg_assemble(m, D))) return rc;
+        T.end(&R.phase_ms[1]);
+        if ((rc = read_out())) return rc;
+        if (it == 0) R.chi2_before = out[orbmi::kEgOutChi];
+        orbmi::eg_lm_begin(L, it, out[orbmi::kEgOutChi]);
+        bool more;
+        do {
+            T.begin();
+            if ((rc = orbmi::launch_eg_factor_solve(m, D, L.lambda))) return rc;
+            T.end(&R.phase_ms[2]);
+            if ((rc = read_out())) return rc;
+            const bool ok2 = out[orbmi::kEgOutFail] == 0;
+            const double scale = ok2 ? out[orbmi::kEgOutScale] : 0.0;
+            double tempChi = 0;
+            if (ok2) {
+                T.begin();
+                if ((rc = orbmi::launch_eg_update(m, D, C.est, C.trial))) return rc;
+                T.end(&R.phase_ms[3]);
+                if ((rc = read_out())) return rc;
+                tempChi = out[orbmi::kEgOutChi];
+            } else {
+                R.status |= ORBMI_EG_SOLVE_FAILED;
+            }
+            if (orbmi::eg_lm_trial(L, ok2, tempChi, scale, &more)) std::swap(C.est, C.trial);  // the step is kept
+            else R.status |= ORBMI_EG_REJECTED;  // est still holds the accepted estimates
+        } while (more);
+        R.trials[it] = L.qmax;
+        R.iterations++;
+        if (orbmi::s3o_lm_end(L)) {
+            stopped = true;
+            break;
+        }
+    }
+    if (stopped) R.status |= ORBMI_EG_TERMINATE;
+    R.chi2_after = L.currentChi;
+    ORBMI_HIP(hipMemcpyAsync(R.vertices, C.est, vb, hipMemcpyDeviceToHost, m.ls()));
+    ORBMI_HIP(hipStreamSynchronize(m.ls()));
+    return ORBMI_OK;
+}
+
+int orbmi_debug_essgraph_linearize(orbmi_matcher* h, const orbmi_essgraph_problem* problem, int32_t* dims,
+                                   int32_t* vert_of, int32_t* col_ptr, int32_t* row_of, double* Hd, double* Ho,
+                                   double* b, double* chi2) {
+    if (!h || !problem || !dims || !essgraph_args_ok(*problem)) return ORBMI_E_ARG;
+    const orbmi_essgraph_problem& P = *problem;
+    const std::vector<orbmi::EgEdge> E = essgraph_edges_of(P);
+    if (!orbmi::eg_args_ok(P.n_vertices, P.fixed, P.n_edges, E.data())) return ORBMI_E_ARG;
+    if (!vert_of) {
+        const orbmi::EgPlan Q = orbmi::eg_plan(P.n_vertices, P.fixed, P.n_edges, E.data());
+        dims[0] = Q.nf;
+        dims[1] = Q.nl;
+        return ORBMI_OK;
+    }
+    if (!col_ptr || !row_of || !Hd || !Ho || !b || !chi2) return ORBMI_E_ARG;
+    Matcher& m = h->m;
+    ORBMI_HIP(hipSetDevice(m.device));
+    m.arena_reset();
+    EssgraphCall C;
+    int rc = essgraph_stage(m, P, E, &C);
+    if (rc) return rc;
+    const orbmi::EgPlan& Q = C.plan;
+    dims[0] = Q.nf;
+    dims[1] = Q.nl;
+    memcpy(vert_of, Q.vert_of.data(), Q.vert_of.size() * sizeof(int32_t));
+    memcpy(col_ptr, Q.col_ptr.data(), Q.col_ptr.size() * sizeof(int32_t));
+    memcpy(row_of, Q.row_of.data(), Q.row_of.size() * sizeof(int32_t));
+    *chi2 = 0;
+    if (Q.ne > 0) {
+        if ((rc = orbmi::launch_eg_linearize(m, C.D, C.est))) return rc;
+        if ((rc = orbmi::launch_eg_assemble(m, C.D))) return rc;
+        ORBMI_HIP(hipMemcpyAsync(chi2, C.D.out + orbmi::kEgOutChi, sizeof(double), hipMemcpyDeviceToHost, m.ls()));
+        if (Q.nf) {
+            ORBMI_HIP(hipMemcpyAsync(Hd, C.D.Hd, (size_t)Q.nf * 49 * sizeof(double), hipMemcpyDeviceToHost, m.ls()));
+            ORBMI_HIP(hipMemcpyAsync(b, C.D.b, (size_t)Q.nf * 7 * sizeof(double), hipMemcpyDeviceToHost, m.ls()));
+        }
+        if (Q.nl) ORBMI_HIP(hipMemcpyAsync(Ho, C.D.Ho, (size_t)Q.nl * 49 * sizeof(double), hipMemcpyDeviceToHost, m.ls()));
+    }
+    ORBMI_HIP(hipStreamSynchronize(m.ls()));
+    return ORBMI_OK;
+}
+
+int orbmi_correct_points_sim3(orbmi_matcher* h, int n_points, const float* points, const int32_t* ref, int n_ref,
+                              const double* Srw, const double* Swr_corrected, float* out_points, int n_poses,
+                              const double* poses, float* out_tcw) {
+    if (!h || n_points < 0 || n_ref < 0 || n_poses < 0) return ORBMI_E_ARG;
+    if (n_points > 0 && (!points || !ref || !Srw || !Swr_corrected || !out_points || n_ref < 1)) return ORBMI_E_ARG;
+    if (n_poses > 0 && (!poses || !out_tcw)) return ORBMI_E_ARG;
+    for (int i = 0; i < n_points; i++)
+        if (ref[i] < 0 || ref[i] >= n_ref) return ORBMI_E_ARG;
+    if (n_points == 0 && n_poses == 0) return ORBMI_OK;
+    Matcher& m = h->m;
+    ORBMI_HIP(hipSetDevice(m.device));
+    m.arena_reset();
+    int rc = 0;
+    std::vector<OutBuf> outs;
+    const float* d_p = dev_in(m, points, 3 * (size_t)n_points, &rc);
+    const int32_t* d_r = dev_in(m, ref, (size_t)n_points, &rc);
+    const orbmi::Sim3d* d_a = dev_in(m, (const orbmi::Sim3d*)Srw, n_points ? (size_t)n_ref : 0, &rc);
+    const orbmi::Sim3d* d_b = dev_in(m, (const orbmi::Sim3d*)Swr_corrected, n_points ? (size_t)n_ref : 0, &rc);
+    const orbmi::Sim3d* d_s = dev_in(m, (const orbmi::Sim3d*)poses, (size_t)n_poses, &rc);
+    if (rc) return rc;
+    float* d_op = n_points ? dev_out(m, out_points, 3 * (size_t)n_points, outs) : nullptr;
+    float* d_ot = n_poses ? dev_out(m, out_tcw, 16 * (size_t)n_poses, outs) : nullptr;
+    if ((n_points && !d_op) || (n_poses && !d_ot)) return ORBMI_E_HIP;
+    if ((rc = orbmi::launch_eg_correct(m, n_points, d_p, d_r, d_a, d_b, d_op, n_poses, d_s, d_ot))) return rc;
+    return finish(m, outs, nullptr, nullptr);
 }
 
 int orbmi_debug_greedy_stats(unsigned long long* out, int reset) {

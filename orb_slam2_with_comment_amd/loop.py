@@ -8,8 +8,14 @@ LoopDetector              DetectLoop: the early add, minScore over the covisible
 detect_and_compute_sim3   DetectLoop, SearchByBoW(KF, KF) per enough-consistent candidate, then
                           sim3.compute_sim3: LoopClosing::Run up to CorrectLoop.
 
+essential_graph_edges     the edge list of Optimizer::OptimizeEssentialGraph (host only).
+propagate_corrected_sim3  CorrectLoop's pose propagation: CorrectedSim3 and NonCorrectedSim3.
+optimize_essential_graph  the edge list, the device pose-graph Levenberg and the correction of
+                          poses and map points: the arithmetic of LoopClosing::CorrectLoop.
+
 The covisibility graph stays the caller's: it comes in as callables (or mappings) from a keyframe
-id to ids.  CorrectLoop and DetectRelocalizationCandidates are not here.
+id to ids.  CorrectLoop's map surgery (Fuse(KF, Scw), MapPoint::Replace, UpdateConnections), global
+BA and DetectRelocalizationCandidates are not here.
 """
 from __future__ import annotations
 
@@ -289,3 +295,196 @@ def detect_and_compute_sim3(detector: LoopDetector, keyframes, loop_points_of, f
     if r["candidate"] is not None and r["accepted"]:
         out["loop_kf"] = ids[r["candidate"]]
     return out
+
+
+# ---- LoopClosing::CorrectLoop: the essential graph -----------------------------------
+# A Sim3 is 8 doubles: q (x y z w), t, s.  A graph is a dict over keyframe ids:
+#   live (n_ids) bool, Tcw (n_ids, 4, 4) float32, parent (n_ids, -1: none),
+#   loop_edges {id: [ids]}, covisibles {id: [ids]} (GetCovisiblesByWeight(100), in its order),
+#   corrected / noncorrected {id: Sim3}, loop_connections {id: {id: weight}}, loop_id, cur_id
+
+class EssGraphInput(C.Structure):
+    """orbmi_essgraph_input (include/orbmi.h)."""
+    _fields_ = [("n_ids", C.c_int32), ("live", C.c_void_p), ("Tcw", C.c_void_p), ("parent", C.c_void_p),
+                ("loop_off", C.c_void_p), ("loop_ids", C.c_void_p), ("cov_off", C.c_void_p), ("cov_ids", C.c_void_p),
+                ("n_corrected", C.c_int32), ("corrected_ids", C.c_void_p), ("corrected", C.c_void_p),
+                ("n_noncorrected", C.c_int32), ("noncorrected_ids", C.c_void_p), ("noncorrected", C.c_void_p),
+                ("lc_off", C.c_void_p), ("lc_ids", C.c_void_p), ("lc_weight", C.c_void_p), ("loop_id", C.c_int32),
+                ("cur_id", C.c_int32)]
+
+
+def _csr(rows, n, weights=False):
+    off, ids, w = [0], [], []
+    for i in range(n):
+        row = rows.get(i, ())
+        for j in row:
+            ids.append(int(j))
+            if weights:
+                w.append(int(row[j]))
+        off.append(len(ids))
+    pad = [0] if not ids else []  # never a NULL array
+    return np.array(off, np.int32), np.array(ids + pad, np.int32), np.array(w + pad, np.int32)
+
+
+def _sim3_table(d):
+    ids = np.array(sorted(d), np.int32)
+    S = np.array([np.asarray(d[int(i)], np.float64).reshape(8) for i in ids], np.float64).reshape(-1, 8)
+    return ids, S
+
+
+def _sim3_from_float_pose(T, backend=None):
+    """g2o::Sim3(Matrix3d, Vector3d, 1.0) of a float 4x4 pose, through the edge rule's vScw."""
+    G = {"live": np.ones(1, bool), "Tcw": np.asarray(T, np.float32).reshape(1, 4, 4), "parent": np.full(1, -1, np.int32),
+         "loop_edges": {}, "covisibles": {}, "corrected": {}, "noncorrected": {}, "loop_connections": {}, "loop_id": 0, "cur_id": 0}
+    return essential_graph_edges(G, backend)[3][0]
+
+
+def _device_edges(G):
+    n = len(G["live"])
+    live = np.ascontiguousarray(np.asarray(G["live"], bool).astype(np.uint8))
+    Tcw = np.ascontiguousarray(G["Tcw"], np.float32).reshape(n, 16)
+    parent = np.ascontiguousarray(G["parent"], np.int32)
+    lo, li, _ = _csr(G["loop_edges"], n)
+    co, ci, _ = _csr(G["covisibles"], n)
+    xo, xi, xw = _csr(G["loop_connections"], n, True)
+    cid, cs = _sim3_table(G["corrected"])
+    nid, ns = _sim3_table(G["noncorrected"])
+    I = EssGraphInput()
+    I.n_ids, I.live, I.Tcw, I.parent = n, live.ctypes.data, Tcw.ctypes.data, parent.ctypes.data
+    I.loop_off, I.loop_ids, I.cov_off, I.cov_ids = lo.ctypes.data, li.ctypes.data, co.ctypes.data, ci.ctypes.data
+    I.n_corrected, I.n_noncorrected = len(cid), len(nid)
+    if len(cid):
+        I.corrected_ids, I.corrected = cid.ctypes.data, cs.ctypes.data
+    if len(nid):
+        I.noncorrected_ids, I.noncorrected = nid.ctypes.data, ns.ctypes.data
+    I.lc_off, I.lc_ids, I.lc_weight = xo.ctypes.data, xi.ctypes.data, xw.ctypes.data
+    I.loop_id, I.cur_id = int(G["loop_id"]), int(G["cur_id"])
+    cap = int(live.sum()) + int(lo[-1]) + int(co[-1]) + int(xo[-1])
+    v0, v1 = np.zeros(max(cap, 1), np.int32), np.zeros(max(cap, 1), np.int32)
+    meas, vScw, ne = np.zeros((max(cap, 1), 8)), np.zeros((n, 8)), C.c_int()
+    check("orbmi_essential_graph_edges",
+          lib().orbmi_essential_graph_edges(C.addressof(I), cap, v0.ctypes.data, v1.ctypes.data, meas.ctypes.data,
+                                            vScw.ctypes.data, C.byref(ne)))
+    return v0[:ne.value].copy(), v1[:ne.value].copy(), meas[:ne.value].copy(), vScw
+
+
+class EssGraphBackend:
+    """The library's operators behind essential_graph_edges / optimize_essential_graph.  A test
+    drives both with an object of the same three methods over the numpy restatement."""
+
+    def __init__(self, matcher=None, device: int = 0):
+        from .optimizer import EssentialGraphOptimizer
+        self.optimizer = EssentialGraphOptimizer(matcher, device)
+
+    def close(self):
+        self.optimizer.close()
+
+    def essential_graph_edges(self, G):
+        return _device_edges(G)
+
+    def optimize_essential_graph(self, vertices, fixed, v0, v1, meas, fix_scale, iterations=20):
+        return self.optimizer.run(vertices, fixed, v0, v1, meas, fix_scale, iterations)
+
+    def correct_points_sim3(self, points, ref_index, Srw, Swr_corrected, poses):
+        return self.optimizer.correct_points_sim3(points, ref_index, Srw, Swr_corrected, poses)
+
+
+def essential_graph_edges(graph, backend=None):
+    """The edge list of Optimizer::OptimizeEssentialGraph (src/Optimizer.cc:862-1053), host only:
+    -> (v0, v1 as keyframe ids, measurements (E, 8), vScw (n_ids, 8)).  Ascending keyframe id
+    wherever the reference iterates in pointer order."""
+    if backend is None:
+        return _device_edges(graph)
+    return backend.essential_graph_edges(graph)
+
+
+def propagate_corrected_sim3(Tcw, cur_id, connected_ids, Scw, backend=None):
+    """LoopClosing::CorrectLoop's pose propagation (src/LoopClosing.cc:546-581): for the current
+    keyframe and every keyframe connected to it, Sic = Tiw * Twc as a Sim3 of scale 1 and
+    CorrectedSiw = Sic * Scw; NonCorrectedSim3 = the poses as they are.  Tcw: (n_ids, 4, 4) float32;
+    Scw: the accepted Sim3 (8) of the current keyframe.  Twc = [Rcw^T | -Rcw^T tcw] in float, the
+    product Tiw * Twc with double accumulators rounded to float once (cv::gemm's for CV_32F).
+    backend: as essential_graph_edges takes it (the Sim3 of a float pose comes from its vScw).
+    -> (corrected {id: Sim3}, noncorrected {id: Sim3})."""
+    Tcw = np.asarray(Tcw, np.float32)
+    Scw = np.asarray(Scw, np.float64).reshape(8)
+    Twc = np.eye(4, dtype=np.float32)
+    Rwc = Tcw[cur_id, :3, :3].T
+    t = Tcw[cur_id, :3, 3]
+    Twc[:3, :3] = Rwc
+    for r in range(3):
+        Twc[r, 3] = -((Rwc[r, 0] * t[0] + Rwc[r, 1] * t[1]) + Rwc[r, 2] * t[2])
+    corrected, nonc = {int(cur_id): Scw.copy()}, {}
+    for i in [int(k) for k in connected_ids if int(k) != int(cur_id)] + [int(cur_id)]:
+        Tiw = Tcw[i]
+        if i != cur_id:
+            A, B = Tiw.astype(np.float64), Twc.astype(np.float64)
+            Tic = np.zeros((4, 4), np.float64)
+            for r in range(4):
+                for c in range(4):
+                    Tic[r, c] = ((A[r, 0] * B[0, c] + A[r, 1] * B[1, c]) + A[r, 2] * B[2, c]) + A[r, 3] * B[3, c]
+            corrected[i] = _sim3_mul(_sim3_from_float_pose(Tic.astype(np.float32), backend), Scw)
+        nonc[i] = _sim3_from_float_pose(Tiw, backend)
+    return corrected, nonc
+
+
+def _sim3_rotate(q, v):
+    """Eigen's quaternion * vector, one rounding per operation in csrc/sim3_opt.h's order."""
+    q = [np.float64(c) for c in q]
+    v = [np.float64(c) for c in v]
+    ux, uy, uz = q[1] * v[2] - q[2] * v[1], q[2] * v[0] - q[0] * v[2], q[0] * v[1] - q[1] * v[0]
+    ux, uy, uz = ux + ux, uy + uy, uz + uz
+    cx, cy, cz = q[1] * uz - q[2] * uy, q[2] * ux - q[0] * uz, q[0] * uy - q[1] * ux
+    return np.array([(v[0] + q[3] * ux) + cx, (v[1] + q[3] * uy) + cy, (v[2] + q[3] * uz) + cz], np.float64)
+
+
+def _sim3_mul(a, b):
+    """Sim3::operator* in csrc/sim3_opt.h's order."""
+    a, b = [np.float64(c) for c in a], [np.float64(c) for c in b]
+    q = [((a[3] * b[0] + a[0] * b[3]) + a[1] * b[2]) - a[2] * b[1], ((a[3] * b[1] + a[1] * b[3]) + a[2] * b[0]) - a[0] * b[2],
+         ((a[3] * b[2] + a[2] * b[3]) + a[0] * b[1]) - a[1] * b[0], ((a[3] * b[3] - a[0] * b[0]) - a[1] * b[1]) - a[2] * b[2]]
+    t = a[7] * _sim3_rotate(a[:4], b[4:7]) + np.array(a[4:7], np.float64)
+    return np.array(q + list(t) + [a[7] * b[7]], np.float64)
+
+
+def _sim3_inverse(a):
+    a = [np.float64(c) for c in a]
+    qc = [-a[0], -a[1], -a[2], a[3]]
+    m = np.float64(-1.) / a[7]
+    return np.array(qc + list(_sim3_rotate(qc, [m * a[4], m * a[5], m * a[6]])) + [np.float64(1.) / a[7]], np.float64)
+
+
+def optimize_essential_graph(graph, fix_scale, points=None, point_ref=None, backend=None, iterations=20):
+    """Optimizer::OptimizeEssentialGraph (src/Optimizer.cc:829-1118) over a graph dict: the edge list,
+    the Levenberg optimisation with the loop keyframe fixed, the SE3 poses [R | t / s] of every live
+    keyframe and the correction of the map points.  points (n, 3) float32 with point_ref (n): the
+    keyframe id each point is corrected through (mnCorrectedReference where CorrectLoop corrected it,
+    else its reference keyframe).  UpdateNormalAndDepth and the map surgery stay the caller's.
+    -> {"Tcw" (n_ids, 4, 4) float32 (live ids replaced), "vertices" (n_ids, 8), "points", "edges":
+    (v0, v1, meas), "vScw", "chi2_before", "chi2_after", "iterations", "trials", "status"}."""
+    own = backend is None
+    be = EssGraphBackend() if own else backend
+    try:
+        v0, v1, meas, vScw = be.essential_graph_edges(graph)
+        live = np.asarray(graph["live"], bool)
+        ids = np.nonzero(live)[0]
+        index = np.full(len(live), -1, np.int32)
+        index[ids] = np.arange(len(ids), dtype=np.int32)
+        r = be.optimize_essential_graph(vScw[ids], int(index[graph["loop_id"]]), index[v0], index[v1], meas, fix_scale, iterations)
+        opt = np.asarray(r["vertices"], np.float64).reshape(-1, 8)
+        Swc = np.array([_sim3_inverse(S) for S in opt], np.float64).reshape(-1, 8)  # vCorrectedSwc
+        P = np.zeros((0, 3), np.float32) if points is None else np.asarray(points, np.float32).reshape(-1, 3)
+        ref = np.zeros(0, np.int32) if points is None else index[np.asarray(point_ref, np.int64)]
+        if len(ref) and (ref < 0).any():
+            raise ValueError("a point's reference keyframe does not live")
+        new_points, T = be.correct_points_sim3(P, ref, vScw[ids], Swc, opt)
+        Tcw = np.array(graph["Tcw"], np.float32).reshape(len(live), 4, 4)
+        Tcw[ids] = T
+        vertices = vScw.copy()
+        vertices[ids] = opt
+        return {"Tcw": Tcw, "vertices": vertices, "points": new_points, "edges": (v0, v1, meas), "vScw": vScw,
+                "chi2_before": r["chi2_before"], "chi2_after": r["chi2_after"], "iterations": r["iterations"],
+                "trials": r["trials"], "status": r["status"]}
+    finally:
+        if own:
+            be.close()

@@ -337,3 +337,112 @@ class Sim3Optimizer:
         matches1[idx[r["inlier"] == 0]] = -1
         self.last = r
         return r["n_in"]
+
+
+class EssGraphProblem(C.Structure):
+    """orbmi_essgraph_problem (include/orbmi.h)."""
+    _fields_ = [("n_vertices", C.c_int32), ("vertices", C.c_void_p), ("fixed", C.c_int32), ("n_edges", C.c_int32),
+                ("v0", C.c_void_p), ("v1", C.c_void_p), ("measurements", C.c_void_p), ("fix_scale", C.c_int32),
+                ("iterations", C.c_int32), ("profile", C.c_int32)]
+
+
+class EssGraphResult(C.Structure):
+    """orbmi_essgraph_result (include/orbmi.h)."""
+    _fields_ = [("vertices", C.c_void_p), ("chi2_before", C.c_double), ("chi2_after", C.c_double), ("iterations", C.c_int32),
+                ("status", C.c_int32), ("trials", C.c_int32 * 32), ("phase_ms", C.c_float * 4)]
+
+
+EG_TERMINATE, EG_SOLVE_FAILED, EG_REJECTED = 1, 2, 4
+
+
+class EssentialGraphOptimizer:
+    """optimizer.optimize(20) of Optimizer::OptimizeEssentialGraph (src/Optimizer.cc:829-1118) on the
+    GPU over arrays: vertices (n, 8) Sim3 as q (x y z w), t, s; edges as vertex indices v0 / v1 and
+    measurements (E, 8).  matcher: an ORBmatcher whose handle, stream and staging arena are used."""
+
+    def __init__(self, matcher=None, device: int = 0):
+        from .matcher import ORBmatcher
+        self._own = matcher is None
+        self.matcher = ORBmatcher(device=device) if matcher is None else matcher
+
+    def close(self):
+        if self._own and self.matcher is not None:
+            self.matcher.close()
+        self.matcher = None
+
+    @staticmethod
+    def _problem(vertices, fixed, v0, v1, meas, fix_scale, iterations, profile=False):
+        keep = (np.ascontiguousarray(vertices, np.float64).reshape(-1, 8), np.ascontiguousarray(v0, np.int32).reshape(-1),
+                np.ascontiguousarray(v1, np.int32).reshape(-1), np.ascontiguousarray(meas, np.float64).reshape(-1, 8))
+        if not (len(keep[1]) == len(keep[2]) == len(keep[3])):
+            raise ValueError("essential-graph edge arrays differ in length")
+        P = EssGraphProblem()
+        P.n_vertices, P.vertices, P.fixed = len(keep[0]), keep[0].ctypes.data if len(keep[0]) else None, int(fixed)
+        ne = len(keep[1])
+        P.n_edges = ne
+        P.v0, P.v1, P.measurements = (keep[1].ctypes.data, keep[2].ctypes.data, keep[3].ctypes.data) if ne else (None, None, None)
+        P.fix_scale, P.iterations, P.profile = int(bool(fix_scale)), int(iterations), int(bool(profile))
+        return P, keep
+
+    def run(self, vertices, fixed, v0, v1, meas, fix_scale, iterations=20, profile=False) -> dict:
+        """-> {"vertices" (n, 8), "chi2_before", "chi2_after", "iterations", "trials" (per iteration),
+        "status" (EG_* or'ed), "phase_ms" (linearise, assemble, factor + solve, update; profile only)}."""
+        P, keep = self._problem(vertices, fixed, v0, v1, meas, fix_scale, iterations, profile)
+        out = np.zeros((max(len(keep[0]), 1), 8), np.float64)
+        R = EssGraphResult()
+        R.vertices = out.ctypes.data
+        check("orbmi_optimize_essential_graph",
+              lib().orbmi_optimize_essential_graph(self.matcher._h, C.addressof(P), C.addressof(R)))
+        return {"vertices": out[:len(keep[0])], "chi2_before": float(R.chi2_before), "chi2_after": float(R.chi2_after),
+                "iterations": int(R.iterations), "trials": [int(t) for t in R.trials[:R.iterations]], "status": int(R.status),
+                "phase_ms": [float(t) for t in R.phase_ms]}
+
+    def linearize(self, vertices, fixed, v0, v1, meas, fix_scale) -> dict:
+        """One buildSystem pass at the given estimates (orbmi_debug_essgraph_linearize), in the
+        library's block storage: {"vert_of", "col_ptr", "row_of", "Hd" (nf, 7, 7), "Ho" (nl, 7, 7),
+        "b" (nf, 7), "chi2"}; `dense()` below spreads it over the free vertices."""
+        P, keep = self._problem(vertices, fixed, v0, v1, meas, fix_scale, 0)
+        dims = np.zeros(2, np.int32)
+        f = lib().orbmi_debug_essgraph_linearize
+        check("orbmi_debug_essgraph_linearize", f(self.matcher._h, C.addressof(P), dims.ctypes.data, None, None, None, None, None, None, None))
+        nf, nl = int(dims[0]), int(dims[1])
+        vert_of, col_ptr, row_of = np.zeros(max(nf, 1), np.int32), np.zeros(nf + 1, np.int32), np.zeros(max(nl, 1), np.int32)
+        Hd, Ho, b, c = np.zeros((max(nf, 1), 7, 7)), np.zeros((max(nl, 1), 7, 7)), np.zeros((max(nf, 1), 7)), C.c_double()
+        check("orbmi_debug_essgraph_linearize",
+              f(self.matcher._h, C.addressof(P), dims.ctypes.data, vert_of.ctypes.data, col_ptr.ctypes.data, row_of.ctypes.data,
+                Hd.ctypes.data, Ho.ctypes.data, b.ctypes.data, C.byref(c)))
+        return {"vert_of": vert_of[:nf], "col_ptr": col_ptr, "row_of": row_of[:nl], "Hd": Hd[:nf], "Ho": Ho[:nl], "b": b[:nf],
+                "chi2": float(c.value)}
+
+    @staticmethod
+    def dense(lin: dict):
+        """The block storage of linearize() as (free vertices ascending, dense H, b)."""
+        free = np.sort(lin["vert_of"])
+        pos = {int(v): k for k, v in enumerate(free)}
+        n = 7 * len(free)
+        H, b = np.zeros((n, n)), np.zeros(n)
+        for c, v in enumerate(lin["vert_of"]):
+            p = pos[int(v)]
+            H[7 * p:7 * p + 7, 7 * p:7 * p + 7] = lin["Hd"][c]
+            b[7 * p:7 * p + 7] = lin["b"][c]
+            for a in range(lin["col_ptr"][c], lin["col_ptr"][c + 1]):
+                q = pos[int(lin["vert_of"][lin["row_of"][a]])]
+                H[7 * q:7 * q + 7, 7 * p:7 * p + 7] = lin["Ho"][a]
+                H[7 * p:7 * p + 7, 7 * q:7 * q + 7] = lin["Ho"][a].T
+        return free, H, b
+
+    def correct_points_sim3(self, points, ref_index, Srw, Swr_corrected, poses):
+        """orbmi_correct_points_sim3: (corrected points (n, 3) float32, Tcw (k, 4, 4) float32 of poses)."""
+        P = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+        r = np.ascontiguousarray(ref_index, np.int32).reshape(-1)
+        A = np.ascontiguousarray(Srw, np.float64).reshape(-1, 8)
+        B = np.ascontiguousarray(Swr_corrected, np.float64).reshape(-1, 8)
+        S = np.ascontiguousarray(poses, np.float64).reshape(-1, 8)
+        if len(r) != len(P) or len(A) != len(B):
+            raise ValueError("point correction arrays differ in length")
+        out, T = np.zeros((max(len(P), 1), 3), np.float32), np.zeros((max(len(S), 1), 4, 4), np.float32)
+        check("orbmi_correct_points_sim3",
+              lib().orbmi_correct_points_sim3(self.matcher._h, len(P), P.ctypes.data if len(P) else None, r.ctypes.data if len(P) else None,
+                                              len(A), A.ctypes.data if len(A) else None, B.ctypes.data if len(B) else None,
+                                              out.ctypes.data, len(S), S.ctypes.data if len(S) else None, T.ctypes.data))
+        return out[:len(P)], T[:len(S)]
