@@ -428,7 +428,7 @@ extern "C" int orbmi_debug_fast_candidates(orbmi_extractor* h, int item, int lev
                             rc_[j] * sizeof(uint2), hipMemcpyDeviceToHost));
     }
     const int count = (int)cand.size();
-    // k_fast's dense array is in cell-completion order; the tags restore the cell loop's order
+    // k_fast2's dense array is in cell-completion order; the tags restore the cell loop's order
     std::sort(cand.begin(), cand.end(), [](const uint2& a, const uint2& b) { return a.y < b.y; });
     int n = 0;
     for (int k = 0; k < count; k++, n++)

@@ -35,7 +35,7 @@ struct CellGeom {
                          // share kFastRegions regions, cell k of the level writes region k % R)
     int level;
     long long roi_off;   // byte offset of the ROI's first pixel in one image's pyramid (level plane,
-                         // border, stride folded in: k_fast needs no LevelGeom load)
+                         // border, stride folded in: k_fast2 needs no LevelGeom load)
     int stride;          // the level's row stride
     int lcell;           // index of the cell within its level
 };
@@ -46,7 +46,7 @@ struct PyrRect { short x0, x1, y0, y1; };  // half-open interior rectangle of on
 struct PyrTile { PyrRect own, need; };     // k_pyramid tile of one level: written to HBM / computed in LDS
 
 constexpr int kOctNodeCap = 2048;  // live quadtree nodes per level held in LDS
-constexpr int kFastRegions = 16;   // candidate regions per level (spreads k_fast's allocation atomics)
+constexpr int kFastRegions = 16;   // candidate regions per level (spreads k_fast2's allocation atomics)
 constexpr int kBlurTW = 128, kBlurTH = 32;  // GaussianBlur output tile
 
 // Grow-only device buffer.
@@ -77,16 +77,9 @@ struct Extractor {
     long long pimg = 0;      // bytes of one padded pyramid
     long long bimg = 0;      // bytes of one blurred pyramid
     int keys_cap = 0, out_cap = 0;
-    bool describe_wave = false;  // ORBMI_DESC=wave: the one-keypoint-per-wave describe kernel
-    bool fast_v1 = false;        // ORBMI_FAST=v1: the per-lane FAST kernel
-    bool fast_split = false;     // ORBMI_FAST=split: k_fast2 with the segment tests and scores as separate stages
-    int blur_mode = -1;          // GaussianBlur (ORBMI_BLUR): -1 by batch, 0 side stream, 1 in the octree launch, 2 after it,
-                                 // 3 side stream after FAST, 4 side stream level by level behind the pyramid
+    int blur_mode = -1;  // GaussianBlur (ORBMI_BLUR): -1 by batch, 0 side stream, 1 in the octree launch, 2 after it
     hipStream_t bstream = nullptr;  // the blur's side stream
-    hipEvent_t ev_pyr = nullptr, ev_blur = nullptr, ev_l0 = nullptr, ev_f0 = nullptr;
-    std::vector<hipEvent_t> ev_lv;   // ORBMI_BLUR=perlevel: level l of the pyramid written
-    std::vector<int> btile_off;      // first blur tile of each level (btiles are level-major), and the end
-    bool fast_early = false;     // ORBMI_FAST_EARLY=1: level 0's FAST on the side stream beside the resize chain
+    hipEvent_t ev_pyr = nullptr, ev_blur = nullptr;
 
     // device buffers (capacity for `bcap` images)
     int bcap = 0;
@@ -99,8 +92,8 @@ struct Extractor {
     uint8_t* d_blur = nullptr;     // blurred levels: interior only, rows of bstride bytes
     int2* d_btiles = nullptr;      // blur tiles: {level, x0 | y0 << 16}
     int nbtiles = 0;
-    int fast_maxw = 0, fast_maxh = 0, fast_wave_bytes = 0;  // largest cell ROI, k_fast's LDS per wave
-    int* d_level_count = nullptr;   // [b][level][region] FAST candidates (k_fast allocates, k_pyr_level0 clears)
+    int fast_maxw = 0, fast_maxh = 0;  // largest cell ROI (k_fast2's LDS per wave)
+    int* d_level_count = nullptr;   // [b][level][region] FAST candidates (k_fast2 allocates, k_pyr_level0 clears)
     int* d_regbase = nullptr;       // [level][region] first slot of each candidate region (per image)
     std::vector<uint32_t> pyr_blob; // k_pyramid parameter blocks, pyr_blob_words per tile
     uint32_t* d_pyr_blob = nullptr;

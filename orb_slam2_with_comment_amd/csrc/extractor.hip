@@ -1,10 +1,15 @@
 // MI355X (gfx950) ORB extractor: ORBextractor::operator() (src/ORBextractor.cc:1043-1105)
-// as five kernel stages over a batch of images resident in HBM:
+// as kernel stages over a batch of images resident in HBM:
 //   k_pyramid                     ComputePyramid            (:1107-1132)    one WG per tile, all levels
-//   k_fast                        cell FAST + NMS + fallback (:778-829)      one WG per cell
-//   k_octree                      DistributeOctTree          (:539-763)      one WG per level
-//   k_describe                    IC_Angle + GaussianBlur + computeOrbDescriptor (:77-147,
-//                                 :1076-1104)                               one wave per keypoint
+//     k_pyr_level0 + k_pyr_resize   the same level by level, for batches > kPyrTiledMaxBatch
+//   k_fast2<48|80>                cell FAST + NMS + fallback (:778-829)      one wave per cell
+//   k_octree                      DistributeOctTree          (:539-763)      one WG per level; up to
+//                                 kFuseBlurMaxOctrees octrees the blur rides in its launch
+//   k_blur                        GaussianBlur               (:1076-1090)    one WG per 128x32 tile,
+//                                 on a side stream beside FAST and the octrees (larger batches)
+//   k_describe4                   IC_Angle + computeOrbDescriptor (:77-147, :1091-1104)
+//                                                                           four keypoints per wave
+// Extractor::run enqueues them in that order.
 // Results are bit-exact with the pinned CPU restatement (oracle/, DESIGN.md "Pinned semantics").
 #include <algorithm>
 #include <cmath>
@@ -17,10 +22,6 @@
 #include "trig_f64.h"
 
 namespace orbmi {
-
-__constant__ signed char c_pattern[256][4];
-__constant__ signed char c_circle[768][2];  // (u, v) of the 749 IC_Angle patch pixels
-__constant__ int c_ncircle;
 
 // ------------------------------------------------------------------------------ pyramid
 // ComputePyramid (src/ORBextractor.cc:1107-1132) in one launch: level 0 = copyMakeBorder(image,
@@ -84,7 +85,7 @@ __device__ inline void pyr_stage(T* dst, int n, F&& load) {
 // halo of any tile), so it follows from blockIdx alone and the image loads go out together with
 // the tile's parameter block (rectangles, level geometry, the resize taps of its need
 // rectangles): one HBM round trip before all levels run out of LDS.
-// It also clears the image's per-level candidate counters (k_fast allocates from them).
+// It also clears the image's per-level candidate counters (k_fast2 allocates from them).
 __global__ __launch_bounds__(kPyrThreads) void k_pyramid(const uint8_t* __restrict__ img, size_t step,
                                                          size_t img_stride, uint8_t* __restrict__ pyr, long long pimg,
                                                          const uint32_t* __restrict__ blobs, int blob_words,
@@ -265,22 +266,8 @@ __device__ inline bool xcd_image_map(int nimg, int& unit, int& img) {
 }
 
 // ------------------------------------------------------------------------------ FAST
-constexpr int kTile = 64;               // max cell ROI edge (wCell+6, hCell+6): list entries are y << 6 | x
+constexpr int kTile = 64;               // max cell ROI edge (wCell+6, hCell+6): it fits k_fast2<80>'s tile
 constexpr int kFastCells = 2;           // waves (cells) per workgroup
-// A wave's LDS (dynamic, sized by the host for the level geometry's largest cell ROI maxW x maxH:
-// ~37 x 37 for the 30-px cells of every level, so a CU holds ~3x the waves of a 64 x 64 sizing):
-//   tile    maxH rows of tsd dwords (the ROI row from its aligned start: tsd = (maxW + 6) / 4)
-//   scores  maxH rows of sp bytes (sp = maxW rounded up to 16)
-//   list    (maxW - 6)(maxH - 6) u16 entries
-struct FastLds { int tsd, sp, list, wave_bytes; };
-__host__ __device__ inline FastLds fast_lds_layout(int maxW, int maxH) {
-    FastLds f;
-    f.tsd = (maxW + 6) / 4;
-    f.sp = (maxW + 15) & ~15;
-    f.list = (maxW - 6) * (maxH - 6);
-    f.wave_bytes = ((4 * f.tsd * maxH + 15) & ~15) + ((maxH * f.sp + 15) & ~15) + ((2 * f.list + 15) & ~15);
-    return f;
-}
 
 // LDS writes of this wave visible to its own later reads (wave-private LDS regions)
 __device__ inline void wave_sync_lds_ex() {
@@ -290,326 +277,41 @@ __device__ inline void wave_sync_lds_ex() {
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
-// The 16 pixels of OpenCV's offsets16 (radius-3 Bresenham circle, (dx, dy)) around (x, y).
-__device__ inline void fast_circle(const uint8_t* t, int pitch, int x, int y, int p[16]) {
-    const int o[16][2] = {{0, 3}, {1, 3}, {2, 2}, {3, 1}, {3, 0}, {3, -1}, {2, -2}, {1, -3},
-                          {0, -3}, {-1, -3}, {-2, -2}, {-3, -1}, {-3, 0}, {-3, 1}, {-2, 2}, {-1, 3}};
-    const uint8_t* c = t + y * pitch + x;
-#pragma unroll
-    for (int k = 0; k < 16; k++) p[k] = c[o[k][1] * pitch + o[k][0]];
-}
-
-// FAST_t's segment test: 9 contiguous circle pixels (the 25-long wrapped scan) all brighter
-// than v + th or all darker than v - th.
-__device__ inline bool fast_segment(int v, const int p[16], int th) {
-    unsigned bright = 0, dark = 0;
-#pragma unroll
-    for (int k = 0; k < 16; k++) {
-        bright |= (unsigned)(p[k] > v + th) << k;
-        dark |= (unsigned)(p[k] < v - th) << k;
-    }
-    auto arc9 = [](unsigned m) {
-        unsigned m2 = m | (m << 16), r = m2;
-#pragma unroll
-        for (int s = 1; s <= 8; s++) r &= m2 >> s;
-        return (r & 0xFFFFu) != 0;
-    };
-    return arc9(bright) || arc9(dark);
-}
-
-// cornerScore<16> (OpenCV fast_score.cpp), d[k] = v - p[k mod 16], k < 25, stored as uchar.
-// For a pixel that passes the segment test at th the value does not depend on th, and the
-// pixel passes at any t >= th exactly when the value is >= t (checked exhaustively against the
-// scalar restatement over 7.5e7 patches): one score per pixel serves both thresholds.
-__device__ inline int fast_corner_score(int v, const int p[16], int th) {
-    int d[25];
-#pragma unroll
-    for (int k = 0; k < 25; k++) d[k] = v - p[k & 15];
-    int a0 = th;
-#pragma unroll
-    for (int k = 0; k < 16; k += 2) {
-        int a = min(d[k + 1], d[k + 2]);
-        a = min(a, d[k + 3]);
-        if (a <= a0) continue;
-        a = min(a, d[k + 4]);
-        a = min(a, d[k + 5]);
-        a = min(a, d[k + 6]);
-        a = min(a, d[k + 7]);
-        a = min(a, d[k + 8]);
-        a0 = max(a0, min(a, d[k]));
-        a0 = max(a0, min(a, d[k + 9]));
-    }
-    int b0 = -a0;
-#pragma unroll
-    for (int k = 0; k < 16; k += 2) {
-        int bb = max(d[k + 1], d[k + 2]);
-        bb = max(bb, d[k + 3]);
-        bb = max(bb, d[k + 4]);
-        bb = max(bb, d[k + 5]);
-        if (bb >= b0) continue;
-        bb = max(bb, d[k + 6]);
-        bb = max(bb, d[k + 7]);
-        bb = max(bb, d[k + 8]);
-        b0 = min(b0, max(bb, d[k]));
-        b0 = min(b0, max(bb, d[k + 9]));
-    }
-    return (-b0 - 1) & 0xFF;
-}
-
 __device__ inline int lanes_below(unsigned long long m) {
     return (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
 }
 
-// One wave per (image, cell), kFastCells cells per workgroup, so every step syncs at wave level
-// only.  The cell ROI (<= 64 x 64) is staged in the wave's LDS as aligned dwords (its first byte
-// at a per-cell offset 0..3).  FAST with nonmax at ini_th, then at min_th when that finds
-// nothing (src/ORBextractor.cc:804-817), as four compaction stages over a row-major pixel list
-// (u16 y << 6 | x, ballot-compacted in place, so the order is FAST_t's emission order):
-//   A  every scored pixel: two cyclically adjacent compass pixels (0, 4, 8, 12) both brighter or
-//      both darker at t = min(ini_th, min_th) -- necessary for a 9-arc (any 9 consecutive of 16
-//      hold two adjacent multiples of 4);
-//   B  the survivors: the full segment test at t;
-//   C  the corners: cornerScore into the cell's score map (with > 64 corners, first only those at
-//      ini_th, found by a second segment test; the others if the cell falls back to min_th);
-//   D  strict 3x3 NMS of the corners at ini_th (score >= ini_th; neighbours below it count 0),
-//      compacted in place; when none survives, the same at min_th.
+// k_fast2: one wave per (image, cell), kFastCells cells per workgroup, so every step syncs at
+// wave level only.  The cell ROI (<= 64 x 64) is staged in the wave's LDS as aligned dwords (its
+// first byte at a per-cell offset 0..3) with a compile-time pitch TS, next to a score map of the
+// same pitch, so every circle / compass / NMS neighbour read is one ds_read_u8 with an immediate
+// offset from the pixel's address.  FAST with nonmax at ini_th, then at min_th when that finds
+// nothing (src/ORBextractor.cc:804-817), as compaction stages over a row-major list of tile
+// offsets (u16 y TS + x, ballot-compacted in place, so the order is FAST_t's emission order):
+//   A    every scored pixel: two cyclically adjacent compass pixels (0, 4, 8, 12) both brighter
+//        or both darker at t -- necessary for a 9-arc (any 9 consecutive of 16 hold two adjacent
+//        multiples of 4); the eight compares are combined as lane masks;
+//   B+C  the survivors: one pass of fast_arc_strength (fast_score.h: packed 16-bit min/max, S > t
+//        is the segment test at t and S - 1 the cornerScore), which both finds the corners and
+//        writes their scores into the map;
+//   D    strict 3x3 NMS of the corners at the threshold (score >= t; neighbours below it count 0,
+//        all eight read unconditionally), compacted in place.
+// A to D run first at ini_th, and at min_th only for a cell with no survivor.  The window bases
+// are kept out of the reads' address folding (lds_window).
 // The survivors go to one of the level's kFastRegions dense candidate regions (cell k of the
 // level: region k % R) at an offset taken with one atomic per cell, as {x | y << 12 | score << 24
 // (x, y relative to minBorder, :820-825), cell << 10 | rank}: the tag orders them as the
 // reference's cell loop does, so their position does not matter.
-__global__ __launch_bounds__(64 * kFastCells) void k_fast(const uint8_t* __restrict__ pyr, long long pimg,
-                                                          const LevelGeom* __restrict__ levels,
-                                                          const CellGeom* __restrict__ cells, int ncells,
-                                                          uint2* __restrict__ cand, int keys_cap,
-                                                          int* __restrict__ level_count, int nlevels, int ini_th,
-                                                          int min_th, int maxW, int maxH) {
-    extern __shared__ uint4 fast_lds[];
-    const int wid = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const FastLds F = fast_lds_layout(maxW, maxH);
-    const int c = blockIdx.x * kFastCells + wid, b = blockIdx.y;
-    if (c >= ncells) return;
-    const CellGeom cg = cells[c];
-    if (cg.w == 0) return;
-    const long long a = b * pimg + cg.roi_off;
-    const int o = (int)(a & 3);  // stride is a multiple of 64: the same offset on every row
-    const unsigned* src = reinterpret_cast<const unsigned*>(pyr + (a - o));
-    const int w = cg.w, h = cg.h, nd = (w + o + 3) >> 2, s4 = cg.stride >> 2;
-    uint8_t* wl = reinterpret_cast<uint8_t*>(fast_lds) + wid * F.wave_bytes;
-    unsigned* t4 = reinterpret_cast<unsigned*>(wl);
-    uint4* scores4 = reinterpret_cast<uint4*>(wl + ((4 * F.tsd * maxH + 15) & ~15));
-    unsigned short* L = reinterpret_cast<unsigned short*>(reinterpret_cast<uint8_t*>(scores4) + ((maxH * F.sp + 15) & ~15));
-    const int TS = 4 * F.tsd, SP = F.sp;
-    {
-        constexpr int kLd = 8;  // loads in flight per lane (a 37 x 37 ROI: 370 dwords, one round)
-        for (int i0 = 0; i0 < nd * h; i0 += 64 * kLd) {
-            unsigned v[kLd];
-#pragma unroll
-            for (int k = 0; k < kLd; k++) {
-                const int i = i0 + lane + 64 * k, r = i / nd, d = i - r * nd;
-                v[k] = r < h ? src[(long long)r * s4 + d] : 0u;
-            }
-#pragma unroll
-            for (int k = 0; k < kLd; k++) {
-                const int i = i0 + lane + 64 * k, r = i / nd, d = i - r * nd;
-                if (r < h) t4[r * F.tsd + d] = v[k];
-            }
-        }
-    }
-    for (int k = lane; k < (maxH * SP) / 16; k += 64) scores4[k] = make_uint4(0u, 0u, 0u, 0u);
-    uint8_t* sc = reinterpret_cast<uint8_t*>(scores4);  // sc[y * SP + x]
-    wave_sync_lds_ex();
-    const uint8_t* tb = reinterpret_cast<const uint8_t*>(t4) + o;  // tb[y * TS + x]
-    const int dw = w - 6, dh = h - 6, npix = dw > 0 && dh > 0 ? dw * dh : 0;
-    const int ti = min(max(ini_th, 0), 255), tm = min(max(min_th, 0), 255), tl = min(ti, tm);
-    // A: compass pre-test over the ROI's scored pixels, row-major
-    int n = 0;
-    if (npix > 0) {
-        int y = lane / dw, x = lane - y * dw;
-        const int q = 64 / dw, r = 64 - q * dw;
-        for (int p0 = 0; p0 < npix; p0 += 64) {
-            bool pass = false;
-            const int X = x + 3, Y = y + 3;
-            if (p0 + lane < npix) {
-                const uint8_t* cp = tb + Y * TS + X;
-                const int v = cp[0], hi = v + tl, lo = v - tl;
-                const int pa = cp[3 * TS], pb = cp[3], pc = cp[-3 * TS], pd = cp[-3];
-                const bool ba = pa > hi, bb = pb > hi, bc = pc > hi, bd = pd > hi;
-                const bool da = pa < lo, db = pb < lo, dc = pc < lo, dd = pd < lo;
-                pass = (ba & bb) | (bb & bc) | (bc & bd) | (bd & ba) | (da & db) | (db & dc) | (dc & dd) | (dd & da);
-            }
-            const unsigned long long m = __ballot(pass);
-            if (pass) L[n + lanes_below(m)] = (unsigned short)(Y << 6 | X);
-            n += __popcll(m);
-            x += r;
-            y += q;
-            if (x >= dw) { x -= dw; y++; }
-        }
-    }
-    wave_sync_lds_ex();
-    // B: full segment test, compacted in place (a lane writes at or below the entry it read)
-    int nc = 0;
-    for (int i0 = 0; i0 < n; i0 += 64) {
-        const int i = i0 + lane;
-        bool pass = false;
-        unsigned short e = 0;
-        if (i < n) {
-            e = L[i];
-            const int X = e & 63, Y = e >> 6;
-            int p[16];
-            fast_circle(tb, TS, X, Y, p);
-            pass = fast_segment(tb[Y * TS + X], p, tl);
-        }
-        const unsigned long long m = __ballot(pass);
-        if (pass) L[nc + lanes_below(m)] = e;
-        nc += __popcll(m);
-    }
-    wave_sync_lds_ex();
-    // B': with more corners than one pass of the wave scores (nc > 64) and ini_th > min_th, the
-    // corners at ini_th among them (segment test again, listed after them, L2 = L + nc, when the
-    // list has room for both): a corner passes at t exactly
-    // when its score is >= t, so the NMS at ini_th needs the scores of those only (the others
-    // count 0 as neighbours); the rest are scored only if the cell falls back to min_th.  With
-    // nc <= 64 the scoring pass costs the wave the same for any subset.
-    const bool split = ti > tl && nc > 64 && 2 * nc <= F.list;
-    unsigned short* L2 = L + nc;
-    unsigned short* LH = L;
-    int nh = nc;
-    if (split) {
-        LH = L2;
-        nh = 0;
-        for (int i0 = 0; i0 < nc; i0 += 64) {
-            const int i = i0 + lane;
-            bool pass = false;
-            unsigned short e = 0;
-            if (i < nc) {
-                e = L[i];
-                const int X = e & 63, Y = e >> 6;
-                int p[16];
-                fast_circle(tb, TS, X, Y, p);
-                pass = fast_segment(tb[Y * TS + X], p, ti);
-            }
-            const unsigned long long m = __ballot(pass);
-            if (pass) L2[nh + lanes_below(m)] = e;
-            nh += __popcll(m);
-        }
-        wave_sync_lds_ex();
-    }
-    // C: scores of the corners (of LH)
-    auto score = [&](const unsigned short* Ls, int ns) {
-        for (int i = lane; i < ns; i += 64) {
-            const unsigned short e = Ls[i];
-            const int X = e & 63, Y = e >> 6;
-            int p[16];
-            fast_circle(tb, TS, X, Y, p);
-            sc[Y * SP + X] = (uint8_t)fast_corner_score(tb[Y * TS + X], p, tl);
-        }
-        wave_sync_lds_ex();
-    };
-    // D: strict NMS at threshold t over Ls, survivors compacted in place
-    auto nms = [&](unsigned short* Ls, int ns, int t) {
-        int kept = 0;
-        for (int i0 = 0; i0 < ns; i0 += 64) {
-            const int i = i0 + lane;
-            bool keep = false;
-            unsigned short e = 0;
-            if (i < ns) {
-                e = Ls[i];
-                const uint8_t* q = sc + (e >> 6) * SP + (e & 63);
-                const int s = q[0];
-                if (s >= t && s != 0) {
-                    auto nb = [&](int off) {
-                        const int u = q[off];
-                        return u >= t ? u : 0;
-                    };
-                    keep = s > nb(-SP - 1) && s > nb(-SP) && s > nb(-SP + 1) && s > nb(-1) && s > nb(1) &&
-                           s > nb(SP - 1) && s > nb(SP) && s > nb(SP + 1);
-                }
-            }
-            const unsigned long long m = __ballot(keep);
-            if (keep) Ls[kept + lanes_below(m)] = e;
-            kept += __popcll(m);
-        }
-        return kept;
-    };
-    score(LH, nh);
-    int total = nms(LH, nh, ti);  // at ini_th, then at min_th if nothing survived
-    const unsigned short* LO = LH;
-    if (total == 0 && tm != ti) {
-        if (split) score(L, nc);
-        total = nms(L, nc, tm);
-        LO = L;
-    }
-    if (total == 0) return;
-    wave_sync_lds_ex();
-    int base = 0;
-    if (lane == 0)
-        base = atomicAdd(&level_count[(b * nlevels + cg.level) * kFastRegions + cg.lcell % kFastRegions], total);
-    base = __shfl(base, 0);
-    uint2* dst = cand + (long long)b * keys_cap + cg.slot_base + base;
-    const unsigned tag = (unsigned)cg.lcell << 10;
-    for (int i = lane; i < total; i += 64) {
-        const unsigned short e = LO[i];
-        const int X = e & 63, Y = e >> 6;
-        dst[i] = make_uint2((uint32_t)(X + cg.sx) | ((uint32_t)(Y + cg.sy) << 12) | ((uint32_t)sc[Y * SP + X] << 24),
-                            tag | (unsigned)i);
-    }
-}
-
-// k_fast2: k_fast with fewer VALU instructions per cell (k_fast issues ≈2,900 per cell and is
-// VALU-issue-bound).  The ROI tile and the score map have a compile-time pitch TS, so every
-// circle / compass / NMS neighbour read is one ds_read_u8 with an immediate offset from the
-// pixel's address, and the list holds tile offsets (y TS + x) rather than packed coordinates;
-// each circle comparison enters the lane's 16-bit mask with one compare and one add-with-carry;
-// the arc test is doubling on the mask (runs of 2, 4, 8, 9).  The compass pre-test combines its
-// eight compares as lane masks.  Measured alternatives (profiles/r04/fast_seg_ab.txt): the arc
-// test bit-sliced across the wave on the scalar unit (79 SALU ops per polarity for 64 pixels)
-// cut the VALU count by 40 % but made the kernel slower, 0.327 vs 0.307 ms per 64 frames: the
-// scalar unit issues at the same per-SIMD rate as the vector unit.  Outputs and their order are
-// k_fast's.  Round 6 (kStrength, the default; ORBMI_FAST=split keeps the stages above for A/B):
-// stages B and C are one pass of fast_arc_strength (fast_score.h: packed 16-bit min/max, S > t is
-// the segment test at t and S - 1 the score), run first at ini_th on the compass survivors at
-// ini_th and at min_th only for a cell with no survivor; the window bases are kept out of the
-// reads' address folding (lds_window), and NMS reads its eight neighbours unconditionally.
-// Config 5: FAST 0.289 -> 0.164 ms per 64 frames (profiles/r06/fastab.txt).
-// m * 2 + (a > b): the compare's lane mask is the add's carry-in (two VALU ops per bit; the
-// compiler's own form is compare, select, shift-or)
-__device__ inline unsigned shift_in_gt(unsigned m, int a, int b) {
-    unsigned r;
-    asm("v_cmp_gt_i32_e32 vcc, %1, %2\n\tv_addc_co_u32_e32 %0, vcc, %3, %3, vcc" : "=v"(r) : "v"(a), "v"(b), "v"(m) : "vcc");
-    return r;
-}
-
-// FAST's arc test on one lane's 16-bit circle mask (bit k = circle pixel k): runs of 2, 4, 8, 9
-// by doubling on m | m << 16 (a cyclic run starting at s < 16 is bits s .. s + 8).
-__device__ inline bool fast_arc9_word(unsigned m) {
-    unsigned x = m | (m << 16);
-    x &= x >> 1;
-    x &= x >> 2;
-    x &= x >> 4;
-    x &= x >> 1;
-    return (x & 0xFFFFu) != 0;
-}
-
-// The segment test of every lane's pixel: cm = the pixel at (X - 3, Y - 3) of the tile (pitch
-// TS), so all 17 reads take non-negative immediate offsets.  The caller masks inactive lanes.
-template <int TS>
-__device__ inline bool fast_segment_lane(const uint8_t* cm, int th) {
-    constexpr int o[16] = {6 * TS + 3, 6 * TS + 4, 5 * TS + 5, 4 * TS + 6, 3 * TS + 6, 2 * TS + 6, TS + 5, 4,
-                           3, 2, TS + 1, 2 * TS, 3 * TS, 4 * TS, 5 * TS + 1, 6 * TS + 2};
-    int p[16];
-#pragma unroll
-    for (int k = 0; k < 16; k++) p[k] = cm[o[k]];
-    const int v = cm[3 * TS + 3], hi = v + th, lo = v - th;
-    unsigned mb = 0, md = 0;
-#pragma unroll
-    for (int k = 15; k >= 0; k--) {
-        mb = shift_in_gt(mb, p[k], hi);
-        md = shift_in_gt(md, lo, p[k]);
-    }
-    return fast_arc9_word(mb) || fast_arc9_word(md);
-}
-
-// fast_arc_strength (fast_score.h) of every lane's pixel, cm as for fast_segment_lane
+// Earlier forms and measured alternatives, none of them in the tree any more: a
+// per-lane kernel with a runtime pitch (~2,900 VALU instructions per cell, VALU-issue-bound);
+// separate segment-test and cornerScore stages (config 5: FAST 0.289 -> 0.164 ms per 64 frames
+// when they became one pass, profiles/r06/fastab.txt); the arc test bit-sliced across the wave on
+// the scalar unit, which cut the VALU count by 40 % but was slower, 0.327 vs 0.307 ms per 64
+// frames, since the scalar unit issues at the same per-SIMD rate as the vector unit
+// (profiles/r04/fast_seg_ab.txt).
+// fast_arc_strength (fast_score.h) of every lane's pixel: cm = the pixel at (X - 3, Y - 3) of the
+// tile (pitch TS), so all 17 reads take non-negative immediate offsets.  The caller masks
+// inactive lanes.
 template <int TS>
 __device__ inline int fast_strength_lane(const uint8_t* cm, int th) {
     constexpr int o[16] = {6 * TS + 3, 6 * TS + 4, 5 * TS + 5, 4 * TS + 6, 3 * TS + 6, 2 * TS + 6, TS + 5, 4,
@@ -634,7 +336,7 @@ __host__ __device__ inline int fast2_wave_bytes(int TS, int maxW, int maxH) {
     return 2 * fast2_tile_bytes(TS, maxH) + ((2 * (maxW - 6) * (maxH - 6) + 15) & ~15);
 }
 
-template <int TS, bool kStrength>
+template <int TS>
 __global__ __launch_bounds__(64 * kFastCells) void k_fast2(const uint8_t* __restrict__ pyr, long long pimg,
                                                            const CellGeom* __restrict__ cells, int c0, int ncells,
                                                            uint2* __restrict__ cand, int keys_cap,
@@ -652,7 +354,7 @@ __global__ __launch_bounds__(64 * kFastCells) void k_fast2(const uint8_t* __rest
     const int o = (int)(a & 3);  // stride is a multiple of 64: the same offset on every row
     const unsigned* src = reinterpret_cast<const unsigned*>(pyr + (a - o));
     const int w = cg.w, h = cg.h, nd = (w + o + 3) >> 2, s4 = cg.stride >> 2;
-    const int tbytes = fast2_tile_bytes(TS, maxH), lcap = (maxW - 6) * (maxH - 6);
+    const int tbytes = fast2_tile_bytes(TS, maxH);
     uint8_t* wl = reinterpret_cast<uint8_t*>(fast_lds) + wid * fast2_wave_bytes(TS, maxW, maxH);
     unsigned* t4 = reinterpret_cast<unsigned*>(wl);
     uint8_t* sc = wl + tbytes;  // scores, sc[y * TS + x]
@@ -728,84 +430,37 @@ __global__ __launch_bounds__(64 * kFastCells) void k_fast2(const uint8_t* __rest
         }
         return kept;
     };
-    int total = 0;
-    const unsigned short* LO = L;
-    if constexpr (kStrength) {
-        // B + C at once: S = fast_arc_strength at t; a corner at t' >= t exactly when S > t', its
-        // score S - 1 whatever t (fast_score.h), so the pass both finds and scores the corners and
-        // NMS reads the map at either threshold (scores below it count 0 there)
-        auto strength = [&](int n, int t) {
-            int nc = 0;
-            for (int i0 = 0; i0 < n; i0 += 64) {
-                const int i = i0 + lane;
-                const unsigned short e = L[min(i, n - 1)];
-                const int S = fast_strength_lane<TS>(tb + lds_window(e, 3 * TS + 3), t);
-                const bool pass = S > t && i < n;
-                const unsigned long long m = __ballot(pass);
-                if (pass) {
-                    L[nc + lanes_below(m)] = e;
-                    sc[e] = (uint8_t)(S - 1);
-                }
-                nc += __popcll(m);
+    // B + C at once: S = fast_arc_strength at t; a corner at t' >= t exactly when S > t', its
+    // score S - 1 whatever t (fast_score.h), so the pass both finds and scores the corners and
+    // NMS reads the map at either threshold (scores below it count 0 there)
+    auto strength = [&](int n, int t) {
+        int nc = 0;
+        for (int i0 = 0; i0 < n; i0 += 64) {
+            const int i = i0 + lane;
+            const unsigned short e = L[min(i, n - 1)];
+            const int S = fast_strength_lane<TS>(tb + lds_window(e, 3 * TS + 3), t);
+            const bool pass = S > t && i < n;
+            const unsigned long long m = __ballot(pass);
+            if (pass) {
+                L[nc + lanes_below(m)] = e;
+                sc[e] = (uint8_t)(S - 1);
             }
-            wave_sync_lds_ex();
-            return nc;
-        };
-        // FAST at ini_th first, from its own compass survivors (a corner at ini_th, and so every
-        // neighbour NMS at ini_th counts, passes the compass at ini_th): about half the candidates
-        // of the compass at min_th.  Only a cell without a survivor runs the min_th pass (the
-        // scores it rewrites are the same values).  With min_th >= ini_th one pass at ini_th
-        // holds the corners of both.
-        const bool two = tm < ti;
-        int nc = strength(compass(two ? ti : tl), two ? ti : tl);
-        total = nms(L, nc, ti);
-        if (total == 0 && tm != ti) {
-            if (two) nc = strength(compass(tm), tm);
-            total = nms(L, nc, tm);
+            nc += __popcll(m);
         }
-    } else {
-        const int n = compass(tl);
-        // B: full segment test at tl, compacted in place (a lane writes at or below the entry it read)
-        auto segment_pass = [&](const unsigned short* Ls, int ns, unsigned short* Ld, int th) {
-            int kept = 0;
-            for (int i0 = 0; i0 < ns; i0 += 64) {
-                const int i = i0 + lane;
-                const unsigned short e = Ls[min(i, ns - 1)];  // the last lanes repeat an entry, masked off
-                const bool pass = fast_segment_lane<TS>(tb + lds_window(e, 3 * TS + 3), th) && i < ns;
-                const unsigned long long m = __ballot(pass);
-                if (pass) Ld[kept + lanes_below(m)] = e;
-                kept += __popcll(m);
-            }
-            wave_sync_lds_ex();
-            return kept;
-        };
-        const int nc = segment_pass(L, n, L, tl);
-        // B': the corners at ini_th among them, listed after them (see k_fast)
-        const bool split = ti > tl && nc > 64 && 2 * nc <= lcap;
-        unsigned short* LH = L;
-        int nh = nc;
-        if (split) {
-            LH = L + nc;
-            nh = segment_pass(L, nc, LH, ti);
-        }
-        // C: cornerScore of the corners
-        auto score = [&](const unsigned short* Ls, int ns) {
-            for (int i = lane; i < ns; i += 64) {
-                const unsigned short e = Ls[i];
-                int p[16];
-                fast_circle(tb + e, TS, 0, 0, p);
-                sc[e] = (uint8_t)fast_corner_score(tb[e], p, tl);
-            }
-            wave_sync_lds_ex();
-        };
-        score(LH, nh);
-        total = nms(LH, nh, ti);
-        LO = LH;
-        if (total == 0 && tm != ti) {
-            if (split) score(L, nc);
-            total = nms(L, nc, tm);
-            LO = L;
-        }
+        wave_sync_lds_ex();
+        return nc;
+    };
+    // FAST at ini_th first, from its own compass survivors (a corner at ini_th, and so every
+    // neighbour NMS at ini_th counts, passes the compass at ini_th): about half the candidates
+    // of the compass at min_th.  Only a cell without a survivor runs the min_th pass (the
+    // scores it rewrites are the same values).  With min_th >= ini_th one pass at ini_th
+    // holds the corners of both.
+    const bool two = tm < ti;
+    int nc = strength(compass(two ? ti : tl), two ? ti : tl);
+    int total = nms(L, nc, ti);
+    if (total == 0 && tm != ti) {
+        if (two) nc = strength(compass(tm), tm);
+        total = nms(L, nc, tm);
     }
     if (total == 0) return;
     wave_sync_lds_ex();
@@ -816,7 +471,7 @@ __global__ __launch_bounds__(64 * kFastCells) void k_fast2(const uint8_t* __rest
     uint2* dst = cand + (long long)b * keys_cap + cg.slot_base + base;
     const unsigned tag = (unsigned)cg.lcell << 10;
     for (int i = lane; i < total; i += 64) {
-        const unsigned short e = LO[i];
+        const unsigned short e = L[i];
         const int Y = e / TS, X = e - Y * TS;
         dst[i] = make_uint2((uint32_t)(X + cg.sx) | ((uint32_t)(Y + cg.sy) << 12) | ((uint32_t)sc[e] << 24),
                             tag | (unsigned)i);
@@ -953,7 +608,7 @@ __device__ __forceinline__ void octree_body(OctShared& S, int level, int b, cons
     uint32_t* NO = node_of + (long long)b * keys_cap + g.key_base;     // node | depth << 16
 
     OCT_STAMP(0, __builtin_amdgcn_s_memtime());
-    // ---- the level's candidates (k_fast's dense array, in cell-completion order): thread t
+    // ---- the level's candidates (k_fast2's dense array, in cell-completion order): thread t
     // holds keys t R .. t R + R - 1 in registers (R = kOctRegKeys; a cell's keys are contiguous,
     // so a thread's increments mostly hit one counter); keys from kOctThreads R on stay in CK
     // with their node in NO.  Nothing below depends on the keys' order except through the tags.
@@ -1545,10 +1200,7 @@ __global__ __launch_bounds__(256) void k_blur(const uint8_t* __restrict__ pyr, u
 // ------------------------------------------------------------------------------ describe
 constexpr int kBR = 18;                 // rotated rBRIEF samples lie within 18 px (pattern radius 18.4)
 constexpr int kBW = 2 * kBR + 1;        // blurred window 37 x 37
-constexpr int kBD = (kBW + 3 + 3) / 4;  // dwords per window row (any start alignment): 10
 constexpr int kUR = 15;                 // IC_Angle patch radius (HALF_PATCH_SIZE)
-constexpr int kUW = 2 * kUR + 1;        // unblurred window 31 x 31
-constexpr int kUD = (kUW + 3 + 3) / 4;  // 9
 
 __device__ inline float fast_atan2_deg(float y, float x) {
     // cv::fastAtan2 (OpenCV 3.x mathfuncs): polynomial in degrees
@@ -1570,118 +1222,6 @@ __device__ inline float fast_atan2_deg(float y, float x) {
     if (x < 0) a = 180.f - a;
     if (y < 0) a = 360.f - a;
     return a;
-}
-
-// One wave per keypoint: the 31x31 unblurred patch (IC_Angle) and the 37x37 blurred window
-// (k_blur output) go to the wave's LDS as aligned dwords covering each window row (the row's
-// first byte sits at a per-window offset 0..3), then 4 ballots give the 256 bits.
-__global__ __launch_bounds__(256) void k_describe(const uint8_t* __restrict__ pyr, const uint8_t* __restrict__ blur,
-                                                  long long pimg, long long bimg, const LevelGeom* __restrict__ levels,
-                                                  int nlevels,
-                                                  const uint2* __restrict__ oct_out, int oct_cap,
-                                                  const int* __restrict__ oct_count,
-                                                  orbmi_keypoint* __restrict__ kps,
-                                                  uint8_t* __restrict__ desc, int* __restrict__ counts,
-                                                  int capacity) {
-    __shared__ unsigned winb[4][kBW * kBD];
-    __shared__ unsigned winu[4][kUW * kUD];
-    const int b = blockIdx.y, wid = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int j = blockIdx.x * 4 + wid;
-    const int* lc = oct_count + b * nlevels;
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-        int t = 0;
-        for (int l = 0; l < nlevels; l++) t += lc[l];
-        counts[b] = t;
-    }
-    int level = -1;
-    for (int l = 0; l < nlevels; l++)
-        if (j >= levels[l].out_base && j < levels[l].out_base + levels[l].out_cap) level = l;
-    // every wave owns its own LDS windows, so only wave-level ordering is needed below
-    if (level < 0) return;
-    const LevelGeom g = levels[level];
-    const int idx = j - g.out_base;
-    if (idx >= lc[level]) return;
-    int off = 0;
-    for (int l = 0; l < level; l++) off += lc[l];
-    const uint2 o = oct_out[(long long)b * oct_cap + j];
-    const int x = o.x & 0xFFFF, y = o.x >> 16;
-    unsigned* wb = winb[wid];
-    unsigned* wu = winu[wid];
-    const long long base = b * pimg + g.off + (long long)(kEdge + y) * g.stride + kEdge + x;
-    const long long sb = b * bimg + g.boff + (long long)(y - kBR) * g.bstride + x - kBR;  // byte address
-    const long long su = base - (long long)kUR * g.stride - kUR;
-    const int ob = (int)(sb & 3), ou = (int)(su & 3);  // first window byte inside the first dword
-    {
-        const unsigned* b4 = reinterpret_cast<const unsigned*>(blur + (sb - ob));
-        const unsigned* u4 = reinterpret_cast<const unsigned*>(pyr + (su - ou));
-        const int bs4 = g.bstride >> 2, us4 = g.stride >> 2;
-        unsigned vb[(kBW * kBD + 63) / 64], vu[(kUW * kUD + 63) / 64];
-#pragma unroll
-        for (int k = 0; k < (kBW * kBD + 63) / 64; k++) {  // all loads first, then the LDS stores
-            const int i = lane + 64 * k, r = i / kBD, c = i - r * kBD;
-            vb[k] = i < kBW * kBD ? b4[(long long)r * bs4 + c] : 0u;
-        }
-#pragma unroll
-        for (int k = 0; k < (kUW * kUD + 63) / 64; k++) {
-            const int i = lane + 64 * k, r = i / kUD, c = i - r * kUD;
-            vu[k] = i < kUW * kUD ? u4[(long long)r * us4 + c] : 0u;
-        }
-#pragma unroll
-        for (int k = 0; k < (kBW * kBD + 63) / 64; k++)
-            if (lane + 64 * k < kBW * kBD) wb[lane + 64 * k] = vb[k];
-#pragma unroll
-        for (int k = 0; k < (kUW * kUD + 63) / 64; k++)
-            if (lane + 64 * k < kUW * kUD) wu[lane + 64 * k] = vu[k];
-    }
-    const uint8_t* wbb = reinterpret_cast<const uint8_t*>(wb) + ob;  // wbb[r * 4 kBD + c] = window (r, c)
-    const uint8_t* wub = reinterpret_cast<const uint8_t*>(wu) + ou;
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0): window stores landed in LDS
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    // IC_Angle on the unblurred level (src/ORBextractor.cc:77-104)
-    int m01 = 0, m10 = 0;
-    for (int i = lane; i < c_ncircle; i += 64) {
-        const int u = c_circle[i][0], v = c_circle[i][1];
-        const int val = wub[(kUR + v) * 4 * kUD + kUR + u];
-        m10 += u * val;
-        m01 += v * val;
-    }
-    m10 = wave_sum_i32(m10);
-    m01 = wave_sum_i32(m01);
-    const float angle = fast_atan2_deg((float)m01, (float)m10);
-    // computeOrbDescriptor on the blurred level (src/ORBextractor.cc:108-147), pinned P6
-    const float ang = angle * (float)(3.14159265358979323846 / 180.0);
-    double sd, cd;  // (float)cos((double)ang), (float)sin((double)ang), checked exhaustively (trig_f64.h)
-    orbmi_sincos_f64((double)ang, &sd, &cd);
-    const float ca = (float)cd, sa = (float)sd;
-    unsigned long long masks[4];
-#pragma unroll
-    for (int kk = 0; kk < 4; kk++) {
-        const int t = kk * 64 + lane;
-        const float px0 = c_pattern[t][0], py0 = c_pattern[t][1];
-        const float px1 = c_pattern[t][2], py1 = c_pattern[t][3];
-        const int c0 = cv_round_f(px0 * ca - py0 * sa), r0 = cv_round_f(px0 * sa + py0 * ca);
-        const int c1 = cv_round_f(px1 * ca - py1 * sa), r1 = cv_round_f(px1 * sa + py1 * ca);
-        const int v0 = wbb[(kBR + r0) * 4 * kBD + kBR + c0];
-        const int v1 = wbb[(kBR + r1) * 4 * kBD + kBR + c1];
-        masks[kk] = __ballot(v0 < v1);
-    }
-    if (off + idx < capacity) {
-        const long long oi = (long long)b * capacity + off + idx;
-        if (lane < 4) reinterpret_cast<unsigned long long*>(desc + oi * 32)[lane] = masks[lane == 0 ? 0 : lane == 1 ? 1 : lane == 2 ? 2 : 3];
-        if (lane == 0) {
-            orbmi_keypoint kp;
-            kp.x = level == 0 ? (float)x : (float)x * g.scale;
-            kp.y = level == 0 ? (float)y : (float)y * g.scale;
-            kp.size = g.size;
-            kp.angle = angle;
-            kp.response = (float)o.y;
-            kp.octave = level;
-            kp.class_id = -1;
-            kps[oi] = kp;
-        }
-    }
 }
 
 // Four keypoints per wave, one DPP row (16 lanes) each: the per-keypoint scalar work -- the
@@ -1894,16 +1434,6 @@ int Extractor::init(int dev, int nf, float sf, int nl, int ini, int mn) {
         umax[v] = v0;
         ++v0;
     }
-    // constant tables: pattern and the IC_Angle circle
-    signed char circ[768][2];
-    int nc = 0;
-    for (int v = -kHalfPatch; v <= kHalfPatch; v++) {
-        const int d = umax[v < 0 ? -v : v];
-        for (int u = -d; u <= d; u++) { circ[nc][0] = (signed char)u; circ[nc][1] = (signed char)v; nc++; }
-    }
-    ORBMI_HIP(hipMemcpyToSymbol(HIP_SYMBOL(c_pattern), ORBMI_PATTERN, sizeof(ORBMI_PATTERN)));
-    ORBMI_HIP(hipMemcpyToSymbol(HIP_SYMBOL(c_circle), circ, sizeof(circ)));
-    ORBMI_HIP(hipMemcpyToSymbol(HIP_SYMBOL(c_ncircle), &nc, sizeof(int)));
     {   // k_describe4's tables: the pattern as (x0, x1, y0, y1) floats, and per 4-B phase ou of
         // the IC patch's first byte the dwords covering each circle row with their byte weights
         float4 pf[256];
@@ -1929,16 +1459,8 @@ int Extractor::init(int dev, int nf, float sf, int nl, int ini, int mn) {
             }
         }
         ORBMI_HIP(hipMemcpyToSymbol(HIP_SYMBOL(c_ictab), ic, sizeof(ic)));
-        const char* e = getenv("ORBMI_DESC");
-        describe_wave = e && !strcmp(e, "wave");
-        e = getenv("ORBMI_FAST");
-        fast_v1 = e && !strcmp(e, "v1");
-        fast_split = e && !strcmp(e, "split");
-        e = getenv("ORBMI_FAST_EARLY");
-        fast_early = e && !strcmp(e, "1");
-        e = getenv("ORBMI_BLUR");
-        blur_mode = !e ? -1 : !strcmp(e, "side") ? 0 : !strcmp(e, "fused") ? 1 : !strcmp(e, "serial") ? 2
-                  : !strcmp(e, "afterfast") ? 3 : !strcmp(e, "perlevel") ? 4 : -1;
+        const char* e = getenv("ORBMI_BLUR");
+        blur_mode = !e ? -1 : !strcmp(e, "side") ? 0 : !strcmp(e, "fused") ? 1 : !strcmp(e, "serial") ? 2 : -1;
     }
     std::vector<float> tab(scale);
     tab.insert(tab.end(), inv_scale.begin(), inv_scale.end());
@@ -1994,7 +1516,7 @@ int Extractor::set_geometry(int r, int c) {
         const float width = (float)(maxBX - minB), height = (float)(maxBY - minB);
         const int nCols = (int)(width / 30.f), nRows = (int)(height / 30.f);
         const int wCell = (int)ceilf(width / nCols), hCell = (int)ceilf(height / nRows);
-        if (wCell + 6 > kTile || hCell + 6 > kTile) return ORBMI_E_UNSUPPORTED;  // list entries y << 6 | x
+        if (wCell + 6 > kTile || hCell + 6 > kTile) return ORBMI_E_UNSUPPORTED;  // k_fast2's tile
         const int cap = ((wCell + 1) / 2) * ((hCell + 1) / 2);
         g.cell_begin = (int)cells.size();
         g.key_base = key;
@@ -2185,19 +1707,15 @@ int Extractor::set_geometry(int r, int c) {
         }
     }
     pimg = off;
-    fast_maxw = 7; fast_maxh = 7;  // k_fast's LDS: the largest cell ROI of the geometry
+    fast_maxw = 7; fast_maxh = 7;  // k_fast2's LDS: the largest cell ROI of the geometry
     for (const CellGeom& cg : cells)
         if (cg.w) { fast_maxw = std::max(fast_maxw, (int)cg.w); fast_maxh = std::max(fast_maxh, (int)cg.h); }
-    fast_wave_bytes = fast_lds_layout(fast_maxw, fast_maxh).wave_bytes;
     bimg = boff;
     btiles.clear();
     for (int l = 0; l < nlevels; l++)
         for (int y0 = 0; y0 < levels[l].H; y0 += kBlurTH)
             for (int x0 = 0; x0 < levels[l].W; x0 += kBlurTW) btiles.push_back(make_int2(l, x0 | (y0 << 16)));
     nbtiles = (int)btiles.size();
-    btile_off.assign(nlevels + 1, 0);
-    for (const int2& t : btiles) btile_off[t.x + 1]++;
-    for (int l = 0; l < nlevels; l++) btile_off[l + 1] += btile_off[l];
     (void)slot;
     keys_cap = key;
     out_cap = outb;
@@ -2244,15 +1762,13 @@ int Extractor::reserve(int batch, int capacity) {
 }
 
 // The side stream and its events, created on first use: only the large batches that put the
-// blur (or the early level-0 FAST) on a side stream need them, and an idle stream per extractor
-// would otherwise count against the process's hardware queues (GPU_MAX_HW_QUEUES) for nothing.
+// blur on a side stream need them, and an idle stream per extractor would otherwise count
+// against the process's hardware queues (GPU_MAX_HW_QUEUES) for nothing.
 int Extractor::ensure_side_stream() {
     if (bstream) return ORBMI_OK;
     ORBMI_HIP(orbmi::stream_create(&bstream, "EXTRACTOR"));
     ORBMI_HIP(hipEventCreateWithFlags(&ev_pyr, hipEventDisableTiming));
     ORBMI_HIP(hipEventCreateWithFlags(&ev_blur, hipEventDisableTiming));
-    ORBMI_HIP(hipEventCreateWithFlags(&ev_l0, hipEventDisableTiming));
-    ORBMI_HIP(hipEventCreateWithFlags(&ev_f0, hipEventDisableTiming));
     return ORBMI_OK;
 }
 
@@ -2266,38 +1782,11 @@ int Extractor::run(const uint8_t* d_images, int batch, size_t step, size_t image
     // a side stream (bstream) beside FAST and the octrees, and the describe waits for it (88.3k
     // vs 84.9k frames/s at config 5).  ORBMI_BLUR=side|fused|serial overrides.
     const int blur_mode = this->blur_mode >= 0 ? this->blur_mode : batch * nlevels <= kFuseBlurMaxOctrees ? 1 : 0;
-    // ORBMI_FAST_EARLY=1: with the level-wise pyramid and the side stream, level 0's FAST runs on
-    // the side stream as soon as level 0 is written, beside the resize chain of levels 1..7.  Off
-    // by default: every kernel here is issue-bound, so the overlap only slowed the resize chain
-    // (0.143 -> 0.222 ms) and config 5 stayed at 89k frames/s (profiles/r04/fast_early_ab.txt).
-    const bool early = batch > kPyrTiledMaxBatch && blur_mode == 0 && !fast_v1 && fast_early &&
-                       levels[0].cell_begin == 0 && nlevels > 1;
-    if (blur_mode == 0 || blur_mode >= 3 || early) {
+    if (blur_mode == 0) {
         const int rc = ensure_side_stream();
         if (rc) return rc;
     }
-    const bool per_level = blur_mode == 4 && batch > kPyrTiledMaxBatch;
-    if (per_level && (int)ev_lv.size() < nlevels) {
-        for (int l = (int)ev_lv.size(); l < nlevels; l++) {
-            hipEvent_t e = nullptr;
-            ORBMI_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-            ev_lv.push_back(e);
-        }
-    }
-    auto launch_fast = [&](int c0, int c1, hipStream_t s) {
-        const dim3 grid((c1 - c0 + kFastCells - 1) / kFastCells, batch), block(64 * kFastCells);
-        if (fast_v1)  // ORBMI_FAST=v1: per-lane bit assembly, runtime tile pitch (A/B)
-            hipLaunchKernelGGL(k_fast, grid, block, kFastCells * fast_wave_bytes, s, d_pyr, pimg, d_levels, d_cells,
-                               ncells, d_cand, keys_cap, d_level_count, nlevels, ini_th, min_th, fast_maxw, fast_maxh);
-        else {
-            const bool narrow = fast_maxw + 3 <= 48;
-            const size_t lds = kFastCells * fast2_wave_bytes(narrow ? 48 : 80, fast_maxw, fast_maxh);
-            auto* kf = fast_split ? (narrow ? k_fast2<48, false> : k_fast2<80, false>)
-                                  : (narrow ? k_fast2<48, true> : k_fast2<80, true>);
-            hipLaunchKernelGGL(kf, dim3(xcd_image_grid(grid.x, batch)), block, lds, s, d_pyr, pimg, d_cells, c0, c1, d_cand,
-                               keys_cap, d_level_count, nlevels, ini_th, min_th, fast_maxw, fast_maxh, batch);
-        }
-    };
+    // ---- pyramid
     if (batch > kPyrTiledMaxBatch) {
         for (int l = 0; l < nlevels; l++) {
             const LevelGeom& g = levels[l];
@@ -2307,29 +1796,12 @@ int Extractor::run(const uint8_t* d_images, int batch, size_t step, size_t image
                 const int lrow = (g.W + 3 + 3 + 15) & ~15;  // an image row from its aligned start
                 hipLaunchKernelGGL(k_pyr_level0, grid, dim3(kPyrBThreads), kPyrBRows * lrow, stream, d_images, step,
                                    image_stride, d_pyr, pimg, g, d_level_count, nlevels, lrow);
-                if (early) {  // level 0's FAST beside the resize chain (it reads level 0 only)
-                    ORBMI_HIP(hipEventRecord(ev_l0, stream));
-                    ORBMI_HIP(hipStreamWaitEvent(bstream, ev_l0, 0));
-                    hipEvent_t ef = prof_begin(ORBMI_STAGE_FAST, bstream);
-                    launch_fast(levels[0].cell_begin, levels[0].cell_end, bstream);
-                    prof_end(ORBMI_STAGE_FAST, ef, bstream);
-                    ORBMI_HIP(hipEventRecord(ev_f0, bstream));
-                }
             } else {
                 const int lrow = levels[l - 1].stride;  // a padded source row (64-B multiple)
                 hipLaunchKernelGGL(k_pyr_resize, grid, dim3(kPyrBThreads), 2 * kPyrBRows * lrow + 8 * g.W, stream, d_pyr, pimg,
                                    levels[l - 1], g, d_xtab + g.xtab_off, d_ytab + g.ytab_off, lrow);
             }
             prof_end(l == 0 ? ORBMI_STAGE_PYR_LEVEL0 : ORBMI_STAGE_PYR_RESIZE, ev);
-            if (per_level) {  // ORBMI_BLUR=perlevel: level l's blur as soon as level l is written (A/B)
-                const int n_l = btile_off[l + 1] - btile_off[l];
-                ORBMI_HIP(hipEventRecord(ev_lv[l], stream));
-                ORBMI_HIP(hipStreamWaitEvent(bstream, ev_lv[l], 0));
-                if (n_l > 0)
-                    hipLaunchKernelGGL(k_blur, dim3(xcd_image_grid(n_l, batch)), dim3(256), 0, bstream, d_pyr, d_blur, pimg,
-                                       bimg, d_levels, d_btiles + btile_off[l], batch);
-                if (l == nlevels - 1) ORBMI_HIP(hipEventRecord(ev_blur, bstream));
-            }
         }
     } else {
         hipEvent_t ev = prof_begin(ORBMI_STAGE_PYR_LEVEL0);  // the whole pyramid
@@ -2339,17 +1811,7 @@ int Extractor::run(const uint8_t* d_images, int batch, size_t step, size_t image
                            pyr_hy, d_level_count, pyr_lds0, pyr_lds_half);
         prof_end(ORBMI_STAGE_PYR_LEVEL0, ev);
     }
-    auto side_blur = [&]() -> int {  // the blur on the side stream from this point of the stream
-        ORBMI_HIP(hipEventRecord(ev_pyr, stream));
-        ORBMI_HIP(hipStreamWaitEvent(bstream, ev_pyr, 0));
-        hipEvent_t eb = prof_begin(ORBMI_STAGE_BLUR, bstream);
-        hipLaunchKernelGGL(k_blur, dim3(xcd_image_grid(nbtiles, batch)), dim3(256), 0, bstream, d_pyr, d_blur, pimg, bimg,
-                           d_levels, d_btiles, batch);
-        prof_end(ORBMI_STAGE_BLUR, eb, bstream);
-        ORBMI_HIP(hipEventRecord(ev_blur, bstream));
-        return ORBMI_OK;
-    };
-    if (blur_mode == 0 || (blur_mode == 4 && !per_level)) {
+    if (blur_mode == 0) {  // side: the blur on the side stream from this point of the stream
         ORBMI_HIP(hipEventRecord(ev_pyr, stream));
         ORBMI_HIP(hipStreamWaitEvent(bstream, ev_pyr, 0));
         hipEvent_t eb = prof_begin(ORBMI_STAGE_BLUR, bstream);
@@ -2358,14 +1820,18 @@ int Extractor::run(const uint8_t* d_images, int batch, size_t step, size_t image
         prof_end(ORBMI_STAGE_BLUR, eb, bstream);
         ORBMI_HIP(hipEventRecord(ev_blur, bstream));
     }
+    // ---- FAST
     hipEvent_t ev = prof_begin(ORBMI_STAGE_FAST);
-    launch_fast(early ? levels[1].cell_begin : 0, ncells, stream);
-    prof_end(ORBMI_STAGE_FAST, ev);
-    if (blur_mode == 3) {  // ORBMI_BLUR=afterfast: beside the octrees only (A/B)
-        const int rc = side_blur();
-        if (rc) return rc;
+    {
+        const bool narrow = fast_maxw + 3 <= 48;
+        const size_t lds = kFastCells * fast2_wave_bytes(narrow ? 48 : 80, fast_maxw, fast_maxh);
+        auto* kf = narrow ? k_fast2<48> : k_fast2<80>;
+        hipLaunchKernelGGL(kf, dim3(xcd_image_grid((ncells + kFastCells - 1) / kFastCells, batch)), dim3(64 * kFastCells), lds,
+                           stream, d_pyr, pimg, d_cells, 0, ncells, d_cand, keys_cap, d_level_count, nlevels, ini_th, min_th,
+                           fast_maxw, fast_maxh, batch);
     }
-    if (early) ORBMI_HIP(hipStreamWaitEvent(stream, ev_f0, 0));
+    prof_end(ORBMI_STAGE_FAST, ev);
+    // ---- octree (+ the fused blur)
     ev = prof_begin(ORBMI_STAGE_OCTREE);
     const bool fused = blur_mode == 1;
     const int blur_blocks = fused ? (nbtiles * batch + 3) / 4 : 0;
@@ -2374,18 +1840,16 @@ int Extractor::run(const uint8_t* d_images, int batch, size_t step, size_t image
                        d_cand, d_level_count, d_regbase, d_node_of, keys_cap, d_oct, out_cap, d_oct_count, d_pyr, d_blur,
                        pimg, bimg, d_btiles, fused ? nbtiles : 0, batch);
     prof_end(ORBMI_STAGE_OCTREE, ev);
-    if (blur_mode == 2) {
+    if (blur_mode == 2) {  // serial
         ev = prof_begin(ORBMI_STAGE_BLUR);
         hipLaunchKernelGGL(k_blur, dim3(xcd_image_grid(nbtiles, batch)), dim3(256), 0, stream, d_pyr, d_blur, pimg, bimg,
                            d_levels, d_btiles, batch);
         prof_end(ORBMI_STAGE_BLUR, ev);
     }
-    if (blur_mode == 0 || blur_mode >= 3) ORBMI_HIP(hipStreamWaitEvent(stream, ev_blur, 0));
+    // ---- describe
+    if (blur_mode == 0) ORBMI_HIP(hipStreamWaitEvent(stream, ev_blur, 0));
     ev = prof_begin(ORBMI_STAGE_DESCRIBE);
-    if (describe_wave)  // ORBMI_DESC=wave: one keypoint per wave (A/B)
-        hipLaunchKernelGGL(k_describe, dim3((out_cap + 3) / 4, batch), dim3(256), 0, stream, d_pyr, d_blur, pimg, bimg,
-                           d_levels, nlevels, d_oct, out_cap, d_oct_count, kps, desc, counts, capacity);
-    else {
+    {
         const int nch = (out_cap + kDescKpWG - 1) / kDescKpWG;
         const int gx = std::max(1, std::min(nch, (kDescTargetWG + batch - 1) / batch));
         hipLaunchKernelGGL(k_describe4, dim3(xcd_image_grid(gx, batch)), dim3(64 * kDescWaves),
@@ -2513,13 +1977,9 @@ void Extractor::release() {
     stream = nullptr;
     if (bstream) (void)hipStreamDestroy(bstream);
     bstream = nullptr;
-    for (hipEvent_t e : ev_lv) (void)hipEventDestroy(e);
-    ev_lv.clear();
     if (ev_pyr) (void)hipEventDestroy(ev_pyr);
     if (ev_blur) (void)hipEventDestroy(ev_blur);
-    if (ev_l0) (void)hipEventDestroy(ev_l0);
-    if (ev_f0) (void)hipEventDestroy(ev_f0);
-    ev_pyr = ev_blur = ev_l0 = ev_f0 = nullptr;
+    ev_pyr = ev_blur = nullptr;
 }
 
 }  // namespace orbmi

@@ -13,9 +13,11 @@
 //                                      B_i D^-1 B_j^T over observation pairs (lists built once),
 //                                      Hpp / b_p summed over the keyframe's edges in the diagonal
 //                                      blocks, b_schur = b_p - sum B D^-1 b_l
-//   k_ba_solve         one block       blocked (6x6) LDL^T of the 6K x 6K reduced system with the
-//                                      right-hand side carried through, back substitution,
+//   k_ba_solve_mfma<T> one block       up to 21 free keyframes: LDL^T of the 6K x 6K reduced system
+//                                      in T x T tiles of 16 on the f64 MFMA, back substitution,
 //                                      trial poses exp(dx) * T, poses' part of computeScale
+//   k_ba_solve         one block       22 .. 30 free keyframes: the same by block Gauss-Jordan on
+//                                      the 6x6 pose blocks, one thread per block
 //   k_ba_update_errors thread / point  back substitution x + dx, trial errors, computeScale, and
 //                                      the linearisation at the trial state into the second
 //                                      linear-system buffer (an accepted trial's next iteration
@@ -78,7 +80,6 @@ struct BaCtl {
     int steps;        // trial steps executed (diagnostics)
     int lin;          // which of the two linear-system buffers holds the current system
     unsigned arrive;  // blocks of k_ba_update_errors finished (the last one runs the control)
-    unsigned arrive_s;  // blocks of k_ba_schur_solve finished (the last one solves)
     unsigned arrive_e;  // blocks of k_ba_activate_edges / k_ba_errors finished (the last one
                         // runs the one-wave tail: the LM state set-up / activeRobustChi2)
     double lambda, ni, currentChi, iniChi;
@@ -143,7 +144,7 @@ struct BaDev {
     double* bp;                // kBaMaxPoses x 6 (k_ba_schur, read by the solve)
     double* S;                 // reduced system: packed upper (kBaPacked), or in k_ba_solve_mfma's
                                // tile layout when mfma_T > 0 (mfma_tile_pos)
-    int mfma_T;                // tiles per dimension of the MFMA solve (0: the VALU solves)
+    int mfma_T;                // tiles per dimension of the MFMA solve (0: k_ba_solve)
     double* bs;                // kBaMaxN
     double* xp;                // kBaMaxN
     double* scal;              // [1] poses' computeScale part, [2] solve ok, [3] lambda used
@@ -888,9 +889,10 @@ __device__ __attribute__((always_inline)) inline void pose_rows_sum(const BaDev&
     __syncthreads();
 }
 
-// (always_inline here and on pose_rows_sum: called from two kernels, the compiler otherwise
-// outlines pose_rows_sum<21> into a function call with a 144-byte stack frame, and k_ba_schur
-// went 16.5 -> 23.3 us)
+// (always_inline here and on pose_rows_sum: while a second kernel called this body the compiler
+// outlined pose_rows_sum<21> into a function call with a 144-byte stack frame, and k_ba_schur
+// went 16.5 -> 23.3 us.  k_ba_schur is the only caller now; the body stays a function of its own
+// because folding it into the kernel changes the generated code)
 __device__ __attribute__((always_inline)) inline void schur_body(BaDev a) {
     // the block's pair structure (static within an optimize()) is loaded before the LM state, so
     // that its two dependent loads overlap the control block's instead of following it
@@ -1103,10 +1105,15 @@ __device__ __attribute__((always_inline)) inline void schur_body(BaDev a) {
 __global__ __launch_bounds__(kSchurThreads) void k_ba_schur(BaDev a) { schur_body(a); }
 
 // ---------------------------------------------------------------- reduced system solve
-// Block Gauss-Jordan on the LDL^T = U^T D U factorisation of the reduced camera system,
-// blocked by the 6x6 pose blocks and held in registers: TPT threads own tile (i, j), i <= j, of
-// the upper triangle, or block i of the right-hand side carried as an extra tile column.  Block
-// step k has two phases and two barriers:
+// Two solves of the reduced camera system remain (the variants measured against them are in
+// DESIGN.md section 5): k_ba_solve_mfma<T> below, for up to kBaSolveMfmaMaxPoses free keyframes,
+// and k_ba_solve here, for the 22 .. kBaMaxPoses that the MFMA solve's 8 tiles of 16 do not
+// hold.  Runner::launch_solve picks by BaDev::mfma_T.
+//
+// k_ba_solve: block Gauss-Jordan on the LDL^T = U^T D U factorisation of the reduced camera
+// system, blocked by the 6x6 pose blocks and held in registers: one thread owns tile (i, j),
+// i <= j, of the upper triangle, or block i of the right-hand side carried as an extra tile
+// column.  Block step k has two phases and two barriers:
 //   B(k)  owners of (k, j > k) form W = U_kk^-T A_kj, U_kj = D_k^-1 W and the normalised pivot
 //         row R_kj = U_kk^-1 U_kj (= A_kk^-1 A_kj) and publish W, U, R (LDS); the right-hand
 //         side tile gives y_k = D_k^-1 U_kk^-T z_k and r_k = U_kk^-1 y_k.  Owners of the
@@ -1116,7 +1123,8 @@ __global__ __launch_bounds__(kSchurThreads) void k_ba_schur(BaDev a) { schur_bod
 //         already normalised: M_ij -= M_ik R_kj, right-hand side r_i -= M_ik r_k.
 // After the last step the right-hand side column holds x: no back substitution.  Same solution
 // as LinearSolverEigen's SimplicialLDLT up to the rounding order.
-constexpr int kBaSolveThreads = 512;  // >= TPT x tiles: 2 x (231 + 21) at np <= 21, 465 + 30 at np <= 30
+constexpr int kBaSolveThreads = 512;  // >= tiles: 465 + 30 at np = kBaMaxPoses
+static_assert(kBaMaxPoses * (kBaMaxPoses + 1) / 2 + kBaMaxPoses <= kBaSolveThreads, "one thread per tile");
 #ifdef ORBMI_SOLVE_TRACE  // tools/solve_trace.hip: s_memtime stamps kept in LDS, copied out at the end
 __device__ unsigned long long g_solve_trace[256];
 #define SOLVE_STAMP_DECL __shared__ unsigned long long tstamp[256]
@@ -1146,13 +1154,6 @@ __device__ inline void wave_sync_lds() {
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// value of the neighbouring lane (lane ^ 1) through DPP quad_perm [1,0,3,2] (no LDS round trip)
-__device__ inline double dpp_xor1(double v) {
-    const int lo = __builtin_amdgcn_mov_dpp(__double2loint(v), 0xB1, 0xF, 0xF, false);
-    const int hi = __builtin_amdgcn_mov_dpp(__double2hiint(v), 0xB1, 0xF, 0xF, false);
-    return __hiloint2double(hi, lo);
 }
 
 // 1 / d: v_rcp_f64 and two Newton steps (the pivots of the reduced system)
@@ -1186,15 +1187,20 @@ __device__ inline bool ldl6(double F[36], double inv6[6]) {
     return !bad;
 }
 
-template <int TPT>  // threads per tile: 2 (np <= 21) or 1 (np <= kBaMaxPoses)
-__global__ __launch_bounds__(kBaSolveThreads) void k_ba_solve(BaDev a) {
+// `inline` is load-bearing: it gives the __shared__ arrays below linkonce linkage, as they had
+// while the kernel was a template.  With internal linkage the compiler splits Ud and Dinv6 into
+// scalars, and the kernel goes from 178 VGPRs to 256 and spills.  (The host pass ignores the
+// keyword on a kernel and says so under -Wcuda-compat.)
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Wcuda-compat"
+inline __global__ __launch_bounds__(kBaSolveThreads) void k_ba_solve(BaDev a) {
+#pragma clang diagnostic pop
     const BaCtl& ctl = *a.ctl;
     if (ctl.done || ctl.gen != a.run_gen) return;
     const int np = ctl.np;
     double lam = a.scal[3];
     const double* __restrict__ T = a.Tb[ctl.cur];
     double* __restrict__ Tt = a.Tb[ctl.cur ^ 1];
-    constexpr int CPT = 6 / TPT;  // tile columns per thread
     SOLVE_STAMP_DECL;
     SOLVE_STAMP(threadIdx.x == 0, 250);
     constexpr int kSlot = 37;  // odd stride in doubles: conflict-free LDS rows
@@ -1205,9 +1211,8 @@ __global__ __launch_bounds__(kBaSolveThreads) void k_ba_solve(BaDev a) {
     __shared__ int fail;
     const int N = 6 * np, nblk = np * (np + 1) / 2;
     const int tid = threadIdx.x;
-    // TPT adjacent threads -> tile (bi, bj) of the upper triangle, or (bi, np) = block bi of
-    // the right-hand side.  Thread h of the tile owns its columns CPT h .. CPT h + CPT - 1.
-    const int tile = tid / TPT, h = tid % TPT, c0 = CPT * h;
+    // thread -> tile (bi, bj) of the upper triangle, or (bi, np) = block bi of the right-hand side
+    const int tile = tid;
     const bool own = tile < nblk + np;
     const bool rhs = own && tile >= nblk;
     int bi = 0, bj = 0;
@@ -1220,11 +1225,11 @@ __global__ __launch_bounds__(kBaSolveThreads) void k_ba_solve(BaDev a) {
         bj = bi + t;
     }
     const bool dg = !rhs && bi == bj;
-    double A[6 * CPT];  // A[r * CPT + cc] = element (r, c0 + cc) of the tile
+    double A[36];  // A[r * 6 + c] = element (r, c) of the tile
     // branch-free loads (clamped addresses, then a select) so that all of them are in flight
 #pragma unroll
-    for (int q = 0; q < 6 * CPT; q++) {
-        const int r = q / CPT, c = c0 + q % CPT;
+    for (int q = 0; q < 36; q++) {
+        const int r = q / 6, c = q % 6;
         const bool mat = own && !rhs && (!dg || c >= r), vec = rhs && c == 0;
         const double* src = vec ? a.bs + 6 * bi + r : a.S + (mat ? packed(6 * bi + r, 6 * bj + c, N) : 0);
         const double v = *src;
@@ -1234,27 +1239,15 @@ __global__ __launch_bounds__(kBaSolveThreads) void k_ba_solve(BaDev a) {
     // the owner of a diagonal tile factors it and publishes U_kk, 1 / D_k
     auto factor_diag = [&]() {
         double F[36];
-        if constexpr (TPT == 2) {
 #pragma unroll
-            for (int q = 0; q < 18; q++) {
-                const double o = dpp_xor1(A[q]);
-                const int r = q / 3, cc = q % 3;
-                F[r * 6 + cc] = h == 0 ? A[q] : o;
-                F[r * 6 + 3 + cc] = h == 0 ? o : A[q];
-            }
-        } else {
-#pragma unroll
-            for (int q = 0; q < 36; q++) F[q] = A[q];
-        }
+        for (int q = 0; q < 36; q++) F[q] = A[q];
         double inv6[6];
         const bool ok = ldl6(F, inv6);
-        if (h == 0) {
 #pragma unroll
-            for (int q = 0; q < 36; q++) Ud[q] = F[q];
+        for (int q = 0; q < 36; q++) Ud[q] = F[q];
 #pragma unroll
-            for (int j = 0; j < 6; j++) Dinv6[j] = inv6[j];
-            if (!ok) fail = 1;
-        }
+        for (int j = 0; j < 6; j++) Dinv6[j] = inv6[j];
+        if (!ok) fail = 1;
     };
     __syncthreads();
     if (own && dg && bi == 0) factor_diag();
@@ -1270,44 +1263,43 @@ __global__ __launch_bounds__(kBaSolveThreads) void k_ba_solve(BaDev a) {
 #pragma unroll
                 for (int s2 = t + 1; s2 < 6; s2++) ud[t][s2] = Ud[t * 6 + s2];
 #pragma unroll
-            for (int cc = 0; cc < CPT; cc++)  // W = U_kk^-T A (unit lower solve)
+            for (int c = 0; c < 6; c++)  // W = U_kk^-T A (unit lower solve)
 #pragma unroll
                 for (int t = 1; t < 6; t++)
 #pragma unroll
-                    for (int s2 = 0; s2 < t; s2++) A[t * CPT + cc] -= ud[s2][t] * A[s2 * CPT + cc];
+                    for (int s2 = 0; s2 < t; s2++) A[t * 6 + c] -= ud[s2][t] * A[s2 * 6 + c];
 #pragma unroll
-            for (int q = 0; q < 6 * CPT; q++) {
-                const int r = q / CPT, c = c0 + q % CPT;
-                Wp[bj * kSlot + r * 6 + c] = A[q];
-                A[q] *= Dinv6[r];
-                Up[bj * kSlot + r * 6 + c] = A[q];
+            for (int q = 0; q < 36; q++) {
+                Wp[bj * kSlot + q] = A[q];
+                A[q] *= Dinv6[q / 6];
+                Up[bj * kSlot + q] = A[q];
             }
 #pragma unroll
-            for (int cc = 0; cc < CPT; cc++)  // R = U_kk^-1 U (unit upper solve, bottom up)
+            for (int c = 0; c < 6; c++)  // R = U_kk^-1 U (unit upper solve, bottom up)
 #pragma unroll
                 for (int t = 4; t >= 0; t--)
 #pragma unroll
-                    for (int s2 = t + 1; s2 < 6; s2++) A[t * CPT + cc] -= ud[t][s2] * A[s2 * CPT + cc];
+                    for (int s2 = t + 1; s2 < 6; s2++) A[t * 6 + c] -= ud[t][s2] * A[s2 * 6 + c];
 #pragma unroll
-            for (int q = 0; q < 6 * CPT; q++) Rp[bj * kSlot + (q / CPT) * 6 + c0 + q % CPT] = A[q];
-            SOLVE_STAMP(bj == k + 1 && h == 0, 4 * k);
+            for (int q = 0; q < 36; q++) Rp[bj * kSlot + q] = A[q];
+            SOLVE_STAMP(bj == k + 1, 4 * k);
         }
         if (own && !rhs && bj == k && bi < k) {  // M_ik, stored transposed like W_ki
 #pragma unroll
-            for (int q = 0; q < 6 * CPT; q++) Mp[bi * kSlot + (c0 + q % CPT) * 6 + q / CPT] = A[q];
+            for (int q = 0; q < 36; q++) Mp[bi * kSlot + (q % 6) * 6 + q / 6] = A[q];
         }
         __syncthreads();
         // ---- A(k): eliminate column k from every other row
         if (own && bj > k && bi != k) {
             // A -= L^T P with L(t, r) = W_ki(t, r) below the pivot or M_ik(r, t) above it, and P =
-            // U_kj or R_kj: 6 CPT independent accumulation chains (the unused lower part of a
+            // U_kj or R_kj: 36 independent accumulation chains (the unused lower part of a
             // diagonal tile and the zero columns of a right-hand-side tile stay harmless)
             const bool below = bi > k;
             const double* Pp = below ? Up : Rp;
             const double* Lp = below ? Wp : Mp;
-            double u[6 * CPT], w[36];
+            double u[36], w[36];
 #pragma unroll
-            for (int q = 0; q < 6 * CPT; q++) u[q] = Pp[bj * kSlot + (q / CPT) * 6 + c0 + q % CPT];
+            for (int q = 0; q < 36; q++) u[q] = Pp[bj * kSlot + q];
 #pragma unroll
             for (int q = 0; q < 36; q++) w[q] = Lp[bi * kSlot + q];  // w[t * 6 + r] = L(t, r)
 #pragma unroll
@@ -1315,10 +1307,10 @@ __global__ __launch_bounds__(kBaSolveThreads) void k_ba_solve(BaDev a) {
 #pragma unroll
                 for (int r = 0; r < 6; r++)
 #pragma unroll
-                    for (int cc = 0; cc < CPT; cc++) A[r * CPT + cc] -= w[t * 6 + r] * u[t * CPT + cc];
-            SOLVE_STAMP(dg && bi == k + 1 && h == 0, 4 * k + 1);
+                    for (int c = 0; c < 6; c++) A[r * 6 + c] -= w[t * 6 + r] * u[t * 6 + c];
+            SOLVE_STAMP(dg && bi == k + 1, 4 * k + 1);
             if (dg && bi == k + 1) factor_diag();
-            SOLVE_STAMP(dg && bi == k + 1 && h == 0, 4 * k + 2);
+            SOLVE_STAMP(dg && bi == k + 1, 4 * k + 2);
         }
         __syncthreads();
         SOLVE_STAMP(tid == 0, 4 * k + 3);
@@ -1329,11 +1321,11 @@ __global__ __launch_bounds__(kBaSolveThreads) void k_ba_solve(BaDev a) {
         if (tid == 0) { a.istat[3] = 0; a.scal[1] = 0; a.scal[2] = 0; }
         return;
     }
-    if (rhs && h == 0) {  // x = the right-hand side column
+    if (rhs) {  // x = the right-hand side column
 #pragma unroll
         for (int r = 0; r < 6; r++) {
-            bs[6 * bi + r] = A[r * CPT];
-            a.xp[6 * bi + r] = A[r * CPT];
+            bs[6 * bi + r] = A[r * 6];
+            a.xp[6 * bi + r] = A[r * 6];
         }
     }
     __syncthreads();
@@ -1356,404 +1348,6 @@ __global__ __launch_bounds__(kBaSolveThreads) void k_ba_solve(BaDev a) {
     if (lane == 0) {
         double sc = 0;
         for (int q = 0; q < N; q++) sc += bs[q] * (lam * bs[q] + a.bp[q]);
-        a.scal[1] = sc;
-        a.scal[2] = 1;
-        a.istat[3] = 1;
-    }
-    SOLVE_STAMP(lane == 0, 253);
-    SOLVE_STAMP_FLUSH();
-}
-
-// The same elimination with the tiles laid out by row pairs, 3 threads per tile (2 tile columns
-// each) and 1 thread per right-hand-side block: wave 0 owns tile row 0, wave w >= 1 rows w and
-// np - w (3 np + 2 <= 64 lanes), so a pivot row, its diagonal tile and its right-hand side sit in
-// one wave.  The pivot row publishes its tiles as they are (A_kj) and normalised (R_kj =
-// A_kk^-1 A_kj, through the LDL^T of A_kk); since W_ki^T U_kj = A_ki^T A_kk^-1 A_kj, every other
-// row then applies the same update A_ij -= L^T R_kj with L = A_ki below the pivot and M_ik above.
-// Step k is one phase and one barrier: every tile applies pivot k; the wave of row k + 1 then
-// publishes its updated diagonal tile, every lane of that wave factors it redundantly (no
-// broadcast of the factor) and the row forms pivot row k + 1, synchronised within the wave only,
-// at raised issue priority; the owners of column k + 1 above the pivot publish M.  The pivot-row
-// and M buffers alternate by parity of k (the readers of step k and the writers for step k + 1
-// overlap).  np <= kBaSolveRowsMaxPoses; larger systems use k_ba_solve<1>.
-constexpr int kBaSolveRowsMaxPoses = 20;
-constexpr int kBaSolveRowsThreads = 64 * (1 + kBaSolveRowsMaxPoses / 2);
-static_assert(3 * kBaSolveRowsMaxPoses + 2 <= 64, "a row pair must fit one wave");
-__device__ inline int solve_rows_wave(int row, int np) { return row <= np - row ? row : np - row; }
-__global__ __launch_bounds__(kBaSolveRowsThreads) void k_ba_solve_rows(BaDev a) {
-    const BaCtl& ctl = *a.ctl;
-    if (ctl.done || ctl.gen != a.run_gen) return;
-    const int np = ctl.np;
-    double lam = a.scal[3];
-    const double* __restrict__ T = a.Tb[ctl.cur];
-    double* __restrict__ Tt = a.Tb[ctl.cur ^ 1];
-    constexpr int CPT = 2;
-    constexpr int kSlot = 38;  // doubles; 16-B aligned rows for b128 access
-    constexpr int kRowSlots = kBaSolveRowsMaxPoses + 1;
-    SOLVE_STAMP_DECL;
-    SOLVE_STAMP(threadIdx.x == 0, 250);
-    __shared__ __attribute__((aligned(16))) double Ap[2][kRowSlots * kSlot], Rp[2][kRowSlots * kSlot];
-    __shared__ __attribute__((aligned(16))) double Mp[2][kBaSolveRowsMaxPoses * kSlot];
-    __shared__ double bs[6 * kBaSolveRowsMaxPoses];
-    __shared__ int fail;
-    const int N = 6 * np;
-    const int tid = threadIdx.x;
-    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
-    // lane -> (bi, bj, h); bj = np is the right-hand side (h = 0 only)
-    const int ra = wv, rb = np - wv;  // rows of this wave (rb only for wv >= 1, rb > ra)
-    const int na = 3 * (np - ra) + 1;
-    int bi = -1, bj = 0, h = 0;
-    if (ra < np && (wv == 0 || ra <= rb)) {
-        int l = lane, r = ra;
-        if (l >= na && wv > 0 && rb > ra) { l -= na; r = rb; }
-        if (l < 3 * (np - r) + 1) {
-            bi = r;
-            bj = l < 3 * (np - r) ? r + l / 3 : np;
-            h = l < 3 * (np - r) ? l % 3 : 0;
-        }
-    }
-    const int c0 = CPT * h;
-    const bool own = bi >= 0;
-    const bool rhs = own && bj == np;
-    const bool dg = own && !rhs && bi == bj;
-    double A[6 * CPT];  // A[r * CPT + cc] = element (r, c0 + cc) of the tile
-#pragma unroll
-    for (int q = 0; q < 6 * CPT; q++) {
-        const int r = q / CPT, c = c0 + q % CPT;
-        const bool mat = own && !rhs && (!dg || c >= r), vec = rhs && c == 0;
-        const double* src = vec ? a.bs + 6 * bi + r : a.S + (mat ? packed(6 * bi + r, 6 * bj + c, N) : 0);
-        const double v = *src;
-        A[q] = (mat || vec) ? v : 0.0;
-    }
-    if (tid == 0) fail = 0;
-    // pivot row k: the diagonal tile's owners publish it, every lane of the wave factors it, then
-    // tiles (k, j > k) and the right-hand side publish A_kj and R_kj into buffer k & 1
-    auto pivot_row = [&](int k) {
-        // the diagonal tile from its three owner lanes (lane base + h holds columns 2h, 2h + 1)
-        // by readlane: no LDS round trip on the elimination's critical path
-        const int base = __builtin_amdgcn_readfirstlane(k == ra ? 0 : na);
-        double F[36], inv6[6];
-#pragma unroll
-        for (int r = 0; r < 6; r++)
-#pragma unroll
-            for (int c = r; c < 6; c++) F[r * 6 + c] = readlane_d(A[r * CPT + c % 2], base + c / 2);
-        const bool ok = ldl6(F, inv6);
-        if (dg && bi == k && h == 0 && !ok) fail = 1;
-        if (!(own && bi == k && bj > k)) return;
-        double* __restrict__ Ao = Ap[k & 1];
-        double* __restrict__ R = Rp[k & 1];
-#pragma unroll
-        for (int q = 0; q < 6 * CPT; q++) Ao[bj * kSlot + (q / CPT) * 6 + c0 + q % CPT] = A[q];
-#pragma unroll
-        for (int cc = 0; cc < CPT; cc++)  // U_kk^-T A (unit lower solve)
-#pragma unroll
-            for (int t = 1; t < 6; t++)
-#pragma unroll
-                for (int s2 = 0; s2 < t; s2++) A[t * CPT + cc] -= F[s2 * 6 + t] * A[s2 * CPT + cc];
-#pragma unroll
-        for (int q = 0; q < 6 * CPT; q++) A[q] *= inv6[q / CPT];  // D^-1
-#pragma unroll
-        for (int cc = 0; cc < CPT; cc++)  // R = U_kk^-1 (unit upper solve, bottom up)
-#pragma unroll
-            for (int t = 4; t >= 0; t--)
-#pragma unroll
-                for (int s2 = t + 1; s2 < 6; s2++) A[t * CPT + cc] -= F[t * 6 + s2] * A[s2 * CPT + cc];
-#pragma unroll
-        for (int q = 0; q < 6 * CPT; q++) R[bj * kSlot + (q / CPT) * 6 + c0 + q % CPT] = A[q];
-    };
-    __syncthreads();
-    if (wv == 0) pivot_row(0);  // prologue: pivot row 0
-    __syncthreads();
-    SOLVE_STAMP(tid == 0, 251);
-    // a failed pivot (fail) is acted on after the loop: the remaining steps then only carry
-    // non-finite values, and no step waits on an LDS read of the flag
-    for (int k = 0; k < np; k++) {
-        const bool crit = k + 1 < np && wv == solve_rows_wave(k + 1, np);  // wave-uniform
-        if (crit) __builtin_amdgcn_s_setprio(3);
-        // ---- A(k): eliminate column k from every other row
-        if (own && bj > k && bi != k) {
-            const double* Lp = bi > k ? Ap[k & 1] : Mp[k & 1];
-            double u[6 * CPT], w[36];
-#pragma unroll
-            for (int q = 0; q < 6 * CPT; q++) u[q] = Rp[k & 1][bj * kSlot + (q / CPT) * 6 + c0 + q % CPT];
-#pragma unroll
-            for (int q = 0; q < 36; q++) w[q] = Lp[bi * kSlot + q];  // w[t * 6 + r] = L(t, r)
-            __builtin_amdgcn_sched_barrier(0);  // all 24 LDS reads in flight before the first FMA
-#pragma unroll
-            for (int t = 0; t < 6; t++)
-#pragma unroll
-                for (int r = 0; r < 6; r++)
-#pragma unroll
-                    for (int cc = 0; cc < CPT; cc++) A[r * CPT + cc] -= w[t * 6 + r] * u[t * CPT + cc];
-        }
-        if (k + 1 < np) {
-            // M_i,k+1 (column k + 1 above its pivot, final after A(k)), stored transposed
-            if (own && !rhs && bj == k + 1 && bi <= k) {
-#pragma unroll
-                for (int q = 0; q < 6 * CPT; q++) Mp[(k + 1) & 1][bi * kSlot + (c0 + q % CPT) * 6 + q / CPT] = A[q];
-            }
-            if (crit) {
-                SOLVE_STAMP(dg && bi == k + 1 && h == 0, 4 * k);
-                pivot_row(k + 1);
-                SOLVE_STAMP(own && bi == k + 1 && rhs, 4 * k + 2);
-                __builtin_amdgcn_s_setprio(0);
-            }
-        }
-        __syncthreads();
-        SOLVE_STAMP(tid == 0, 4 * k + 3);
-    }
-    if (fail) {  // pop: trial poses = current ones, computeScale = 0
-        for (int k = tid; k < a.nkf; k += blockDim.x)
-            for (int q = 0; q < 8; q++) Tt[8 * k + q] = T[8 * k + q];
-        if (tid == 0) { a.istat[3] = 0; a.scal[1] = 0; a.scal[2] = 0; }
-        return;
-    }
-    if (rhs) {  // x = the right-hand side column
-#pragma unroll
-        for (int r = 0; r < 6; r++) {
-            bs[6 * bi + r] = A[r * CPT];
-            a.xp[6 * bi + r] = A[r * CPT];
-        }
-    }
-    __syncthreads();
-    if (tid >= 64) return;
-    SOLVE_STAMP(lane == 0, 252);
-    // trial poses T_t = exp(x_p) * T (VertexSE3Expmap::oplusImpl) and the poses' part of
-    // computeScale, sum x_p (lambda x_p + b_p) in index order
-    for (int k = lane; k < a.nkf; k += 64) {
-        const int pi = a.pose_idx[k];
-        if (pi >= 0) {
-            double u[6];
-#pragma unroll
-            for (int q = 0; q < 6; q++) u[q] = bs[6 * pi + q];
-            se3_oplus(u, T + 8 * k, Tt + 8 * k);
-        } else {
-            for (int q = 0; q < 8; q++) Tt[8 * k + q] = T[8 * k + q];
-        }
-    }
-    double sc = 0;  // lane partials in index order, then a fixed-order wave sum
-    for (int q = lane; q < N; q += 64) sc += bs[q] * (lam * bs[q] + a.bp[q]);
-    sc = wave_sum(sc);
-    if (lane == 0) {
-        a.scal[1] = sc;
-        a.scal[2] = 1;
-        a.istat[3] = 1;
-    }
-    SOLVE_STAMP(lane == 0, 253);
-    SOLVE_STAMP_FLUSH();
-}
-
-// k_ba_solve_rows' elimination with the pivot rows formed by a dedicated wave P (the last one),
-// so that the chain from pivot row k to pivot row k + 1 holds no LDS round trip of the update and
-// no wave switch.  P's lanes are column slices (lane 3 j + h: tile column j, columns 2h, 2h + 1;
-// lane 3 np: the right-hand side) and hold, during step k, row k + 1:
-//   step k, P:    A_{k+1,j} -= A_{k,k+1}^T R_{k,j} with R_k kept in P's registers from step k - 1
-//                 and A_{k,k+1} read back from the pivot-row buffer P wrote; then the LDL^T of the
-//                 updated diagonal tile (readlane) and pivot row k + 1 (A and R) into buffer
-//                 (k + 1) & 1; row k + 2 arrives from its owner through LDS at the start of step
-//                 k + 1 (its owner writes it during step k, after applying pivot k).
-//   step k, bulk: the owners of row k load R_k (the pivot row, now normalised) into their
-//                 registers; every other row except k + 1 (P's) applies pivot k as before.
-// One barrier per step.  np <= kBaSolveRowsMaxPoses.
-constexpr int kBaSolvePipeThreads = kBaSolveRowsThreads + 64;
-__global__ __launch_bounds__(kBaSolvePipeThreads) void k_ba_solve_pipe(BaDev a) {
-    const BaCtl& ctl = *a.ctl;
-    if (ctl.done || ctl.gen != a.run_gen) return;
-    const int np = ctl.np;
-    double lam = a.scal[3];
-    const double* __restrict__ T = a.Tb[ctl.cur];
-    double* __restrict__ Tt = a.Tb[ctl.cur ^ 1];
-    constexpr int CPT = 2;
-    constexpr int kSlot = 38;
-    constexpr int kRowSlots = kBaSolveRowsMaxPoses + 1;
-    constexpr int kPivotWave = kBaSolveRowsThreads / 64;
-    SOLVE_STAMP_DECL;
-    SOLVE_STAMP(threadIdx.x == 0, 250);
-    __shared__ __attribute__((aligned(16))) double Ap[2][kRowSlots * kSlot], Rp[2][kRowSlots * kSlot];
-    __shared__ __attribute__((aligned(16))) double Nx[2][kRowSlots * kSlot];  // row k + 2 for P
-    __shared__ __attribute__((aligned(16))) double Mp[2][kBaSolveRowsMaxPoses * kSlot];
-    __shared__ double bs[6 * kBaSolveRowsMaxPoses];
-    __shared__ int fail;
-    const int N = 6 * np;
-    const int tid = threadIdx.x;
-    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
-    const bool P = wv == kPivotWave;
-    // bulk lanes: the row-pair layout of k_ba_solve_rows; P lanes: column slices
-    int bi = -1, bj = 0, h = 0;
-    const int ra = wv, rb = np - wv, na = 3 * (np - ra) + 1;
-    if (P) {
-        if (lane <= 3 * np) {
-            bj = lane < 3 * np ? lane / 3 : np;
-            h = lane < 3 * np ? lane % 3 : 0;
-        }
-    } else if (ra < np && (wv == 0 || ra <= rb)) {
-        int l = lane, r = ra;
-        if (l >= na && wv > 0 && rb > ra) { l -= na; r = rb; }
-        if (l < 3 * (np - r) + 1) {
-            bi = r;
-            bj = l < 3 * (np - r) ? r + l / 3 : np;
-            h = l < 3 * (np - r) ? l % 3 : 0;
-        }
-    }
-    const int c0 = CPT * h;
-    const bool own = bi >= 0;
-    const bool rhs = bj == np;
-    const bool plane = P && lane <= 3 * np;  // a P lane with a column slice
-    // element (r, c0 + cc) of tile (row, bj) from the packed system (upper part of a diagonal tile)
-    auto load_tile = [&](int row, double* A) {
-        const bool dg = !rhs && row == bj;
-#pragma unroll
-        for (int q = 0; q < 6 * CPT; q++) {
-            const int r = q / CPT, c = c0 + q % CPT;
-            const bool mat = !rhs && bj >= row && (!dg || c >= r), vec = rhs && c == 0;
-            const double* src = vec ? a.bs + 6 * row + r : a.S + (mat ? packed(6 * row + r, 6 * bj + c, N) : 0);
-            const double v = *src;
-            A[q] = (mat || vec) ? v : 0.0;
-        }
-    };
-    double A[6 * CPT];   // bulk: its tile slice; P: row k + 1's slice
-    double Rk[6 * CPT];  // P: R_{k,bj} slice (pivot row k, normalised)
-#pragma unroll
-    for (int q = 0; q < 6 * CPT; q++) { A[q] = 0.0; Rk[q] = 0.0; }
-    if (own) load_tile(bi, A);
-    if (tid == 0) fail = 0;
-    // P: factor the diagonal tile of the row it holds (row k), publish A_k and R_k into buffer
-    // k & 1, keep R_k in Rk
-    auto pivot = [&](int k) {
-        const int base = 3 * k;
-        double F[36], inv6[6];
-#pragma unroll
-        for (int r = 0; r < 6; r++)
-#pragma unroll
-            for (int c = r; c < 6; c++) F[r * 6 + c] = readlane_d(A[r * CPT + c % 2], base + c / 2);
-        const bool ok = ldl6(F, inv6);
-        if (lane == 0 && !ok) fail = 1;
-        double R[6 * CPT];
-#pragma unroll
-        for (int q = 0; q < 6 * CPT; q++) R[q] = A[q];
-#pragma unroll
-        for (int cc = 0; cc < CPT; cc++)
-#pragma unroll
-            for (int t = 1; t < 6; t++)
-#pragma unroll
-                for (int s2 = 0; s2 < t; s2++) R[t * CPT + cc] -= F[s2 * 6 + t] * R[s2 * CPT + cc];
-#pragma unroll
-        for (int q = 0; q < 6 * CPT; q++) R[q] *= inv6[q / CPT];
-#pragma unroll
-        for (int cc = 0; cc < CPT; cc++)
-#pragma unroll
-            for (int t = 4; t >= 0; t--)
-#pragma unroll
-                for (int s2 = t + 1; s2 < 6; s2++) R[t * CPT + cc] -= F[t * 6 + s2] * R[s2 * CPT + cc];
-        if (plane && bj > k) {
-            double* __restrict__ Ao = Ap[k & 1];
-            double* __restrict__ Ro = Rp[k & 1];
-#pragma unroll
-            for (int q = 0; q < 6 * CPT; q++) {
-                Ao[bj * kSlot + (q / CPT) * 6 + c0 + q % CPT] = A[q];
-                Ro[bj * kSlot + (q / CPT) * 6 + c0 + q % CPT] = R[q];
-            }
-        }
-#pragma unroll
-        for (int q = 0; q < 6 * CPT; q++) Rk[q] = R[q];
-    };
-    __syncthreads();
-    if (P && np > 0) {  // prologue: row 0 -> pivot row 0; row 1 stays in A for step 0
-        __builtin_amdgcn_s_setprio(3);
-        if (plane) load_tile(0, A);
-        pivot(0);
-        if (np > 1 && plane) load_tile(1, A);
-    }
-    __syncthreads();
-    SOLVE_STAMP(tid == 0, 251);
-    for (int k = 0; k < np; k++) {
-        if (P) {
-            if (k + 1 < np) {
-                if (k >= 1 && plane) {  // row k + 1 with pivots < k applied, from its owner
-#pragma unroll
-                    for (int q = 0; q < 6 * CPT; q++) A[q] = Nx[(k - 1) & 1][bj * kSlot + (q / CPT) * 6 + c0 + q % CPT];
-                }
-                double w[36];  // L = A_{k,k+1} (w[t * 6 + r] = L(t, r)), as P published it
-#pragma unroll
-                for (int q = 0; q < 36; q++) w[q] = Ap[k & 1][(k + 1) * kSlot + q];
-                __builtin_amdgcn_sched_barrier(0);
-                if (plane && bj > k) {
-#pragma unroll
-                    for (int t = 0; t < 6; t++)
-#pragma unroll
-                        for (int r = 0; r < 6; r++)
-#pragma unroll
-                            for (int cc = 0; cc < CPT; cc++) A[r * CPT + cc] -= w[t * 6 + r] * Rk[t * CPT + cc];
-                }
-                SOLVE_STAMP(lane == 0, 4 * k);
-                pivot(k + 1);
-                SOLVE_STAMP(lane == 0, 4 * k + 2);
-            }
-        } else if (own) {
-            if (bi == k) {  // pivot row k: its normalised tiles
-                if (bj > k) {
-#pragma unroll
-                    for (int q = 0; q < 6 * CPT; q++) A[q] = Rp[k & 1][bj * kSlot + (q / CPT) * 6 + c0 + q % CPT];
-                }
-            } else if (bj > k && bi != k + 1) {
-                const double* Lp = bi > k ? Ap[k & 1] : Mp[k & 1];
-                double u[6 * CPT], w[36];
-#pragma unroll
-                for (int q = 0; q < 6 * CPT; q++) u[q] = Rp[k & 1][bj * kSlot + (q / CPT) * 6 + c0 + q % CPT];
-#pragma unroll
-                for (int q = 0; q < 36; q++) w[q] = Lp[bi * kSlot + q];
-                __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                for (int t = 0; t < 6; t++)
-#pragma unroll
-                    for (int r = 0; r < 6; r++)
-#pragma unroll
-                        for (int cc = 0; cc < CPT; cc++) A[r * CPT + cc] -= w[t * 6 + r] * u[t * CPT + cc];
-                if (bi == k + 2) {  // P's row at step k + 1
-#pragma unroll
-                    for (int q = 0; q < 6 * CPT; q++) Nx[k & 1][bj * kSlot + (q / CPT) * 6 + c0 + q % CPT] = A[q];
-                }
-            }
-            if (k + 1 < np && !rhs && bj == k + 1 && bi <= k) {  // M_{i,k+1}, stored transposed
-#pragma unroll
-                for (int q = 0; q < 6 * CPT; q++) Mp[(k + 1) & 1][bi * kSlot + (c0 + q % CPT) * 6 + q / CPT] = A[q];
-            }
-        }
-        __syncthreads();
-        SOLVE_STAMP(tid == 0, 4 * k + 3);
-    }
-    if (P) __builtin_amdgcn_s_setprio(0);
-    if (fail) {  // pop: trial poses = current ones, computeScale = 0
-        for (int k = tid; k < a.nkf; k += blockDim.x)
-            for (int q = 0; q < 8; q++) Tt[8 * k + q] = T[8 * k + q];
-        if (tid == 0) { a.istat[3] = 0; a.scal[1] = 0; a.scal[2] = 0; }
-        return;
-    }
-    if (own && rhs) {  // x = the right-hand side column
-#pragma unroll
-        for (int r = 0; r < 6; r++) {
-            bs[6 * bi + r] = A[r * CPT];
-            a.xp[6 * bi + r] = A[r * CPT];
-        }
-    }
-    __syncthreads();
-    if (tid >= 64) return;
-    SOLVE_STAMP(lane == 0, 252);
-    for (int k = lane; k < a.nkf; k += 64) {
-        const int pi = a.pose_idx[k];
-        if (pi >= 0) {
-            double u[6];
-#pragma unroll
-            for (int q = 0; q < 6; q++) u[q] = bs[6 * pi + q];
-            se3_oplus(u, T + 8 * k, Tt + 8 * k);
-        } else {
-            for (int q = 0; q < 8; q++) Tt[8 * k + q] = T[8 * k + q];
-        }
-    }
-    double sc = 0;
-    for (int q = lane; q < N; q += 64) sc += bs[q] * (lam * bs[q] + a.bp[q]);
-    sc = wave_sum(sc);
-    if (lane == 0) {
         a.scal[1] = sc;
         a.scal[2] = 1;
         a.istat[3] = 1;
@@ -2241,30 +1835,6 @@ __device__ __attribute__((always_inline)) inline void solve_mfma_body(const BaDe
 template <int T>
 __global__ __launch_bounds__(kBaMfmaThreads) void k_ba_solve_mfma(BaDev a) { solve_mfma_body<T>(a); }
 
-// The Schur complement and the MFMA solve in one launch: the Schur blocks as k_ba_schur, then the
-// last block to finish (arrival counter; device-scope release / acquire, so every block's tiles
-// are visible to it) runs the solve with its first four waves.  One launch per trial fewer.
-template <int T>
-__global__ __launch_bounds__(kSchurThreads) void k_ba_schur_solve(BaDev a) {
-    {
-        const BaCtl& ctl = *a.ctl;
-        if (ctl.done || ctl.gen != a.run_gen) return;  // the same for every block
-    }
-    schur_body(a);
-    __shared__ int last;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        __threadfence();
-        last = atomicAdd(&a.ctl->arrive_s, 1u) == gridDim.x - 1;
-    }
-    __syncthreads();
-    if (!last) return;
-    __threadfence();
-    if (threadIdx.x == 0) a.ctl->arrive_s = 0;
-    if (threadIdx.x >= kBaMfmaThreads) return;
-    solve_mfma_body<T>(a);
-}
-
 // ---------------------------------------------------------------- Levenberg control
 // fixed-order sum of n partials by one wave (lane l: l, l + 64, ...; then a fixed xor tree,
 // lane 0's value broadcast): deterministic run to run
@@ -2543,10 +2113,8 @@ struct orbmi_ba {
     hipEvent_t up_done = nullptr;  // the last upload from h_stage has been read
     // the graph upload's own stream (created at the first call): the copy depends on nothing
     // enqueued ahead of LocalBA on `stream` (a LocalMapping chain's searches), so it runs beside
-    // that work and `stream` waits for up_done only.  ORBMI_BA_UPLOAD=inline keeps the copy in
-    // stream order (A/B runs)
+    // that work and `stream` waits for up_done only
     hipStream_t up_stream = nullptr;
-    bool up_beside = true;
     uint8_t* h_out = nullptr;      // pinned staging of the results (poses, positions, erase flags)
     size_t cap_out = 0;
     orbmi::BaCtl* h_ctl = nullptr;  // pinned readback of the LM control block
@@ -2589,44 +2157,40 @@ inline bool stop_set(const volatile int* stop) { return stop && __atomic_load_n(
 // (which all read the Hpl blocks of keyframe ra's edges) go to ids of one residue mod 8 -- one XCD
 // under the round-robin dispatch, so their re-reads of those blocks hit one L2 (speed only).
 // Rows are dealt to the 8 residues largest first onto the least loaded; pairs beyond a residue's
-// ids take the ids left over, in increasing order.  rowmajor: blk_id[l] = l (A/B runs).
+// ids take the ids left over, in increasing order.
 // Every block id in [0, nblk) must name exactly one pair: an id no pair took would leave its
 // blk_kf entry to whatever the pinned staging buffer last held, and the pair kernels index
 // pose_idx / kf_start with it (the round-4 r04x illegal address, from a work-in-progress form of
 // this table, on the first call that reused a larger graph's staging buffer).  So the table is
 // checked before it is used: false = not a permutation (never, by construction; tested for
 // every nf by tests/test_capi_exports.py through orbmi_debug_ba_schur_blocks).
-bool ba_block_table(int nf, bool rowmajor, std::vector<int>& blk_id) {
+bool ba_block_table(int nf, std::vector<int>& blk_id) {
     const int nblk = nf * (nf + 1) / 2;
     blk_id.assign(std::max(nblk, 1), -1);
-    if (rowmajor) {
-        for (int x = 0; x < nblk; x++) blk_id[x] = x;
-    } else {
-        const int R = 8;
-        std::vector<int> load(R, 0), grp(std::max(nf, 1));
-        for (int r = 0; r < nf; r++) {  // row r holds nf - r pairs: already largest first
-            const int g = (int)(std::min_element(load.begin(), load.end()) - load.begin());
-            grp[r] = g;
-            load[g] += nf - r;
+    const int R = 8;
+    std::vector<int> load(R, 0), grp(std::max(nf, 1));
+    for (int r = 0; r < nf; r++) {  // row r holds nf - r pairs: already largest first
+        const int g = (int)(std::min_element(load.begin(), load.end()) - load.begin());
+        grp[r] = g;
+        load[g] += nf - r;
+    }
+    std::vector<int> next(R);
+    for (int g = 0; g < R; g++) next[g] = g;
+    std::vector<char> used(std::max(nblk, 1), 0);
+    std::vector<int> spill;
+    int l = 0;
+    for (int ra = 0; ra < nf; ra++)
+        for (int rb = ra; rb < nf; rb++, l++) {
+            const int g = grp[ra];
+            if (next[g] < nblk) { blk_id[l] = next[g]; used[next[g]] = 1; next[g] += R; }
+            else spill.push_back(l);
         }
-        std::vector<int> next(R);
-        for (int g = 0; g < R; g++) next[g] = g;
-        std::vector<char> used(std::max(nblk, 1), 0);
-        std::vector<int> spill;
-        int l = 0;
-        for (int ra = 0; ra < nf; ra++)
-            for (int rb = ra; rb < nf; rb++, l++) {
-                const int g = grp[ra];
-                if (next[g] < nblk) { blk_id[l] = next[g]; used[next[g]] = 1; next[g] += R; }
-                else spill.push_back(l);
-            }
-        int free_id = 0;
-        for (int x : spill) {
-            while (free_id < nblk && used[free_id]) free_id++;
-            if (free_id >= nblk) return false;
-            blk_id[x] = free_id;
-            used[free_id] = 1;
-        }
+    int free_id = 0;
+    for (int x : spill) {
+        while (free_id < nblk && used[free_id]) free_id++;
+        if (free_id >= nblk) return false;
+        blk_id[x] = free_id;
+        used[free_id] = 1;
     }
     std::vector<char> hit(std::max(nblk, 1), 0);
     for (int x = 0; x < nblk; x++) {
@@ -2649,24 +2213,17 @@ struct Runner {
     orbmi_ba& h;
     BaDev a;
     const volatile int* stop;
-    bool solve_rows;  // nf <= kBaSolveRowsMaxPoses: k_ba_solve_rows, else k_ba_solve<1>
-    bool solve_pipe;  // k_ba_solve_pipe (a dedicated pivot wave) in place of k_ba_solve_rows
-                      // (ORBMI_BA_SOLVE=rows selects the latter, for A/B runs)
-    int mfma_tiles;   // > 0: k_ba_solve_mfma<mfma_tiles> (nf <= kBaSolveMfmaMaxPoses, the default)
 
-    bool fuse_schur = false;  // k_ba_schur_solve (ORBMI_BA_FUSE=1; measured slower than two launches)
-    void launch_mfma() {
-        const dim3 gs(a.nblk + kSchurKfSplit * a.nf + 1);
-        switch (mfma_tiles) {
-#define ORBMI_MFMA_CASE(T_)                                                                                      \
-    case T_:                                                                                                     \
-        if (fuse_schur) hipLaunchKernelGGL(k_ba_schur_solve<T_>, gs, dim3(kSchurThreads), 0, h.stream, a);       \
-        else hipLaunchKernelGGL(k_ba_solve_mfma<T_>, dim3(1), dim3(kBaMfmaThreads), 0, h.stream, a);             \
-        break;
+    // the reduced-system solve: k_ba_solve_mfma<a.mfma_T> when mfma_T > 0, otherwise k_ba_solve
+    void launch_solve() {
+        static_assert((6 * kBaSolveMfmaMaxPoses + 15) / 16 <= 8, "a case per tile count below");
+        switch (a.mfma_T) {
+#define ORBMI_MFMA_CASE(T_) \
+    case T_: hipLaunchKernelGGL(k_ba_solve_mfma<T_>, dim3(1), dim3(kBaMfmaThreads), 0, h.stream, a); break;
             ORBMI_MFMA_CASE(1) ORBMI_MFMA_CASE(2) ORBMI_MFMA_CASE(3) ORBMI_MFMA_CASE(4)
             ORBMI_MFMA_CASE(5) ORBMI_MFMA_CASE(6) ORBMI_MFMA_CASE(7) ORBMI_MFMA_CASE(8)
 #undef ORBMI_MFMA_CASE
-            default: break;
+            default: hipLaunchKernelGGL(k_ba_solve, dim3(1), dim3(kBaSolveThreads), 0, h.stream, a); break;
         }
     }
 
@@ -2697,15 +2254,10 @@ struct Runner {
     // when that optimize() is done or not the current one
     void step(int gen) {
         a.run_gen = gen;
-        if (a.nblk > 0 && !(mfma_tiles > 0 && fuse_schur))  // (+ the MFMA solve's padding block)
+        if (a.nblk > 0)  // (+ the MFMA solve's padding block)
             hipLaunchKernelGGL(k_ba_schur, dim3(a.nblk + kSchurKfSplit * a.nf + (a.mfma_T > 0)), dim3(kSchurThreads), 0,
                                h.stream, a);
-        if (mfma_tiles > 0)
-            launch_mfma();
-        else if (solve_rows && solve_pipe)
-            hipLaunchKernelGGL(k_ba_solve_pipe, dim3(1), dim3(kBaSolvePipeThreads), 0, h.stream, a);
-        else if (solve_rows) hipLaunchKernelGGL(k_ba_solve_rows, dim3(1), dim3(kBaSolveRowsThreads), 0, h.stream, a);
-        else hipLaunchKernelGGL(k_ba_solve<1>, dim3(1), dim3(kBaSolveThreads), 0, h.stream, a);
+        launch_solve();
         hipLaunchKernelGGL(k_ba_update_errors, dim3(a.nb_q), dim3(kBaUpdThreads), 0, h.stream, a);
     }
 
@@ -2748,8 +2300,6 @@ int orbmi_ba_create(int device, orbmi_ba** out) {
         return ORBMI_E_HIP;
     }
     *b->h_stop = 0;
-    const char* up_env = getenv("ORBMI_BA_UPLOAD");
-    b->up_beside = !(up_env && !strcmp(up_env, "inline"));
     *out = b;
     return ORBMI_OK;
 }
@@ -2779,7 +2329,7 @@ int orbmi_debug_ba_schur_blocks(int nf, int* table, int cap, int* n_out) {
     *n_out = nb;
     if (cap < nb || !table) return ORBMI_E_CAP;
     std::vector<int> blk_id;
-    if (!ba_block_table(nf, false, blk_id)) return ORBMI_E_UNSUPPORTED;
+    if (!ba_block_table(nf, blk_id)) return ORBMI_E_UNSUPPORTED;
     std::vector<int> ra_of(std::max(nblk, 1)), rb_of(std::max(nblk, 1)), l_of(std::max(nblk, 1));
     for (int ra = 0, l = 0; ra < nf; ra++)
         for (int rb = ra; rb < nf; rb++, l++) { ra_of[blk_id[l]] = ra; rb_of[blk_id[l]] = rb; l_of[blk_id[l]] = l; }
@@ -2870,7 +2420,7 @@ int orbmi_local_bundle_adjustment(orbmi_ba* b, const orbmi_ba_problem* P, orbmi_
     if (nblk_ll > (1 << 20)) return ORBMI_E_UNSUPPORTED;
     const int nblk = (int)nblk_ll;
     std::vector<int> blk_id;
-    if (!ba_block_table(nf, getenv("ORBMI_BA_SCHUR_ROWMAJOR") != nullptr, blk_id)) return ORBMI_E_UNSUPPORTED;
+    if (!ba_block_table(nf, blk_id)) return ORBMI_E_UNSUPPORTED;
     auto blk_of = [nf, &blk_id](int ra, int rb) { return blk_id[ra * nf - ra * (ra - 1) / 2 + (rb - ra)]; };
     // ---- one device arena; the graph and its index arrays go up in one copy
     const int nb_e = std::max(1, (ne + kBaBlock - 1) / kBaBlock), nb_p = std::max(1, (npt + kBaBlock - 1) / kBaBlock);
@@ -2959,14 +2509,10 @@ int orbmi_local_bundle_adjustment(orbmi_ba* b, const orbmi_ba_problem* P, orbmi_
     uint8_t* B = h.d_buf;
     tr.mark("host_index");
     // (the arena's previous reader, the last call's solve, finished before that call returned)
-    hipStream_t us = s;
-    if (h.up_beside) {
-        if (!h.up_stream) ORBMI_HIP(orbmi::stream_create(&h.up_stream, "BA"));
-        us = h.up_stream;
-    }
-    ORBMI_HIP(hipMemcpyAsync(B, S, up_bytes, hipMemcpyHostToDevice, us));
-    ORBMI_HIP(hipEventRecord(h.up_done, us));
-    if (us != s) ORBMI_HIP(hipStreamWaitEvent(s, h.up_done, 0));
+    if (!h.up_stream) ORBMI_HIP(orbmi::stream_create(&h.up_stream, "BA"));
+    ORBMI_HIP(hipMemcpyAsync(B, S, up_bytes, hipMemcpyHostToDevice, h.up_stream));
+    ORBMI_HIP(hipEventRecord(h.up_done, h.up_stream));
+    ORBMI_HIP(hipStreamWaitEvent(s, h.up_done, 0));
     const size_t out_bytes = o_oerase + (size_t)std::max(ne, 1) - o_otcw;  // tcw, pos, erase (aligned)
     if (out_bytes > h.cap_out) {
         if (h.h_out) (void)hipHostFree(h.h_out);
@@ -3020,15 +2566,10 @@ int orbmi_local_bundle_adjustment(orbmi_ba* b, const orbmi_ba_problem* P, orbmi_
     a.Hpp = (double*)(B + o_Hpp); a.bp = (double*)(B + o_bp);
     a.S = (double*)(B + o_S); a.bs = (double*)(B + o_bs); a.xp = (double*)(B + o_xp);
     a.scal = (double*)(B + o_scal); a.istat = (int*)(B + o_istat);
-    const char* sv = getenv("ORBMI_BA_SOLVE");
-    // the MFMA solve for nf <= kBaSolveMfmaMaxPoses (ORBMI_BA_SOLVE=pipe / rows: the VALU solves)
-    const bool valu_solve = sv && (!strcmp(sv, "pipe") || !strcmp(sv, "rows"));
-    a.mfma_T = (!valu_solve && nf <= kBaSolveMfmaMaxPoses) ? std::max(1, (6 * nf + 15) / 16) : 0;
-    Runner r{h, a, stop, nf <= kBaSolveRowsMaxPoses, !(sv && !strcmp(sv, "rows")), a.mfma_T};
-    {
-        const char* fz = getenv("ORBMI_BA_FUSE");
-        r.fuse_schur = fz && !strcmp(fz, "1");
-    }
+    // the one solver decision: k_ba_solve_mfma<mfma_T> up to kBaSolveMfmaMaxPoses free keyframes
+    // (6 nf unknowns padded to mfma_T tiles of 16), k_ba_solve beyond (Runner::step launches it)
+    a.mfma_T = nf <= kBaSolveMfmaMaxPoses ? std::max(1, (6 * nf + 15) / 16) : 0;
+    Runner r{h, a, stop};
     unsigned char* out_erase = B + o_oerase;
     const int nb_all = std::max(1, (std::max(std::max(nkf, npt), ne) + kBaBlock - 1) / kBaBlock);
     hipLaunchKernelGGL(k_ba_setup, dim3(nb_all), dim3(kBaBlock), 0, s, a, a.Tb[0], a.Xb[0], out_erase);

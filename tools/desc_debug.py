@@ -1,6 +1,6 @@
 """Keypoint / descriptor diff of the device extractor against the oracle on one synthetic frame:
 the first differing rows per field and the descriptor bit-difference histogram.
-python tools/desc_debug.py   (ORBMI_DESC=wave selects the one-keypoint-per-wave describe)"""
+python tools/desc_debug.py"""
 import os
 import sys
 

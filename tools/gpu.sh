@@ -26,13 +26,11 @@
 #   native[_async]   tools/native_probe.py (sync / concurrent LocalMapping)
 #   nativeprof[_async] its rocprofv3 kernel stats
 #   lmprobe          tools/lm_chain_probe.py (per-call split of the LocalMapping chain)
-#   solvetrace[=VAR=1]  per-step split of the reduced-system solve (tools/ubench/solve_trace)
+#   solvetrace       per-step split of k_ba_solve (tools/ubench/solve_trace)
 #   mfma_pmc         MFMA counters of tools/ubench/mfma_schur (build it first)
 #   ab=A,B           bench A/B of two library builds (ORBMI_LIB paths), 3 alternations
 #   abbatch=A,B      the same in --mode batch (config 5)
 #   envab=VAR=VALUE  the default bench without / with an environment knob, 3 alternations
-#   descab           config 5: four keypoints per wave in k_describe vs one (ORBMI_DESC=wave)
-#   fastab           config 5: bit-sliced k_fast2 vs the per-lane k_fast (ORBMI_FAST=v1)
 #   blurab           config 5: GaussianBlur on a side stream / in the octree launch / after it
 TAG=${1:-run}
 shift
@@ -129,10 +127,9 @@ for step in "$@"; do
             run concur 300 python tools/concur_breakdown.py 3; grep -v "^{" $OUT/concur.log | tee $P/concur_breakdown.txt; tail -1 $OUT/concur.log > $P/concur_breakdown.json;;
         lmprobe)
             run lmprobe 300 python tools/lm_chain_probe.py 20; tail -14 $OUT/lmprobe.log;;
-        solvetrace|solvetrace=*)
-            # per-step cycle split of the reduced-system solve (tools/ubench/solve_trace, built beforehand)
-            v=${step#solvetrace}; v=${v#=}
-            run solvetrace$v 60 env $v ./tools/ubench/solve_trace 20; cat $OUT/solvetrace$v.log;;
+        solvetrace)
+            # per-step cycle split of k_ba_solve (tools/ubench/solve_trace, built beforehand)
+            run solvetrace 60 ./tools/ubench/solve_trace 27; cat $OUT/solvetrace.log;;
         solvebin=*)
             # a solve_trace build variant: solvebin=NAME runs tools/ubench/solve_trace_NAME
             b=${step#solvebin=}
@@ -221,11 +218,10 @@ for step in "$@"; do
             done;;
         mfmatrace|mfmatrace=*)
             # per-panel split of the MFMA reduced-system solve (tools/ubench/mfma_solve_trace, built
-            # beforehand) and the VALU pivot-wave solve on the same system
+            # beforehand)
             np_=${step#mfmatrace}; np_=${np_#=}; np_=${np_:-20}
             run mfmatrace$np_ 60 ./tools/ubench/mfma_solve_trace $np_; cat $OUT/mfmatrace$np_.log
-            PIPE=1 run mfmatrace_pipe$np_ 60 ./tools/ubench/mfma_solve_trace $np_; cat $OUT/mfmatrace_pipe$np_.log
-            cat $OUT/mfmatrace$np_.log $OUT/mfmatrace_pipe$np_.log > $P/mfma_solve_trace_np$np_.txt;;
+            cp $OUT/mfmatrace$np_.log $P/mfma_solve_trace_np$np_.txt;;
         ubench=*)
             # a microbenchmark binary under tools/ubench (built beforehand)
             b=${step#ubench=}
@@ -235,16 +231,6 @@ for step in "$@"; do
             run fetchcal_f 90 timeout -s KILL 60 rocprofv3 --pmc FETCH_SIZE --kernel-trace -f csv -d $OUT/fetchcal_f -o f -- ./tools/ubench/fetch_calib
             run fetchcal_w 90 timeout -s KILL 60 rocprofv3 --pmc WRITE_SIZE --kernel-trace -f csv -d $OUT/fetchcal_w -o w -- ./tools/ubench/fetch_calib
             python3 tools/fetch_calib_report.py $OUT/fetchcal_f $OUT/fetchcal_w | tee $P/fetch_calibration.txt;;
-        lbasolve)
-            # config 3: the MFMA solve fused with the Schur complement, the MFMA solve alone, the
-            # VALU pivot-wave solve
-            ms() { tail -1 $OUT/$1.log | python -c 'import json,sys; print(json.load(sys.stdin)["ms_per_step"])'; }
-            for i in 1 2 3; do
-                ORBMI_BA_SOLVE=mfma ORBMI_BA_FUSE=1 run lbasolve_fused_$i 200 python bench.py --mode lba --steps 50 --warmup 10 --no-cpu-baseline
-                ORBMI_BA_SOLVE=mfma run lbasolve_mfma_$i 200 python bench.py --mode lba --steps 50 --warmup 10 --no-cpu-baseline
-                ORBMI_BA_SOLVE=pipe run lbasolve_pipe_$i 200 python bench.py --mode lba --steps 50 --warmup 10 --no-cpu-baseline
-                echo "fused $(ms lbasolve_fused_$i)  mfma $(ms lbasolve_mfma_$i)  pipe $(ms lbasolve_pipe_$i)" | tee -a $OUT/lbasolve.txt
-            done; cp $OUT/lbasolve.txt $P/;;
         mfmapmc|mfmapmc_*)
             # MFMA issue / busy counters per kernel over a short bench run (one pass)
             m=${step#mfmapmc}; m=${m#_}; m=${m:-lba}
@@ -277,31 +263,6 @@ for step in "$@"; do
                 ORBMI_PRIO_LM=default ORBMI_PRIO_MATCHER=default ORBMI_PRIO_POSE=default ORBMI_PRIO_EXTRACTOR=default run prio_flat_$i 300 python bench.py --mode system --no-cpu-baseline
                 echo "tracking high / LM low: $(v prio_hl_$i) | all default: $(v prio_flat_$i)" | tee -a $OUT/prio.txt
             done;;
-        schurxcd)
-            # LocalBA (config 3): Schur blocks grouped by row onto one XCD (default) vs row-major,
-            # 3 alternations, plus FETCH_SIZE of each layout
-            ms() { tail -1 $OUT/$1.log | python -c 'import json,sys; print(json.load(sys.stdin)["ms_per_step"])'; }
-            for i in 1 2 3; do
-                run sx_xcd_$i 200 python bench.py --mode lba --steps 50 --warmup 10 --no-cpu-baseline
-                ORBMI_BA_SCHUR_ROWMAJOR=1 run sx_row_$i 200 python bench.py --mode lba --steps 50 --warmup 10 --no-cpu-baseline
-                echo "xcd rows $(ms sx_xcd_$i)  row-major $(ms sx_row_$i)" | tee -a $OUT/schurxcd.txt
-            done
-            run sx_fetch_xcd 300 timeout -s KILL 240 rocprofv3 --pmc FETCH_SIZE --kernel-trace -f csv -d $OUT/sx_fetch_xcd -o f -- python3 bench.py --mode lba --steps 10 --warmup 2 --no-cpu-baseline
-            ORBMI_BA_SCHUR_ROWMAJOR=1 run sx_fetch_row 300 timeout -s KILL 240 rocprofv3 --pmc FETCH_SIZE --kernel-trace -f csv -d $OUT/sx_fetch_row -o f -- python3 bench.py --mode lba --steps 10 --warmup 2 --no-cpu-baseline
-            for v in xcd row; do
-                f=$(find $OUT/sx_fetch_$v -name "*counter_collection.csv" | head -1)
-                python3 -c "import csv,collections,sys; d=collections.defaultdict(list); [d[r['Kernel_Name'][:40]].append(float(r['Counter_Value'])) for r in csv.DictReader(open(sys.argv[1])) if r['Counter_Name']=='FETCH_SIZE']; [print(sys.argv[2], k, len(v), round(2*sum(v)/len(v)/1024,3), 'MB (2 x FETCH_SIZE)') for k,v in sorted(d.items()) if 'ba_' in k]" $f $v | tee -a $OUT/schurxcd.txt
-            done
-            cp $OUT/schurxcd.txt $P/;;
-        descab)
-            # config 5 batch: the four-keypoints-per-wave describe (default) vs one keypoint per
-            # wave (ORBMI_DESC=wave), 2 alternations
-            v() { tail -1 $OUT/$1.log | python -c 'import json,sys; d=json.load(sys.stdin); print(d["value"], d["stage_ms_per_launch"])'; }
-            for i in 1 2; do
-                run descab_4_$i 300 python bench.py --full --mode batch --steps 20 --warmup 4 --no-cpu-baseline
-                ORBMI_DESC=wave run descab_w_$i 300 python bench.py --full --mode batch --steps 20 --warmup 4 --no-cpu-baseline
-                echo "4/wave: $(v descab_4_$i) | 1/wave: $(v descab_w_$i)" | tee -a $OUT/descab.txt
-            done; cp $OUT/descab.txt $P/;;
         octtrace)
             # k_octree phase trace of every level (tools/octree_trace, built in-tree on the CPU) on a
             # config-5 frame (synthetic EuRoC-shaped 752x480, 5000 features)
@@ -314,27 +275,6 @@ for step in "$@"; do
             python -c "import numpy as np; from orb_slam2_with_comment_amd import synth; np.ascontiguousarray(synth.stereo_pair(synth.KITTI, 0)[0], np.uint8).tofile('$OUT/kitti0.u8')"
             run octab_new 120 ./tools/octree_trace $OUT/kitti0.u8 376 1241 2000 && run octab_old 120 ./tools/octree_trace_old $OUT/kitti0.u8 376 1241 2000
             for v in new old; do echo "== $v"; grep -E "== level|total" $OUT/octab_$v.log; done | tee $P/octree_ab_kitti.txt;;
-        fastab)
-            # config 5 batch: k_fast2 with the one-pass arc strength (default) vs its separate
-            # segment-test and score stages (ORBMI_FAST=split), 3 alternations
-            v() { tail -1 $OUT/$1.log | python -c 'import json,sys; d=json.load(sys.stdin); print(d["value"], d["stage_ms_per_launch"]["fast"])'; }
-            for i in 1 2 3; do
-                run fastab_s_$i 300 python bench.py --full --mode batch --steps 20 --warmup 4 --no-cpu-baseline
-                ORBMI_FAST=split run fastab_p_$i 300 python bench.py --full --mode batch --steps 20 --warmup 4 --no-cpu-baseline
-                echo "one pass: $(v fastab_s_$i) | split: $(v fastab_p_$i)" | tee -a $OUT/fastab.txt
-            done; cp $OUT/fastab.txt $P/;;
-        fastseg)
-            # config 5 batch: k_fast2's arc-test split (ORBMI_FAST_SEG=0 scalar, 1 per lane, 2 mixed)
-            # and the per-lane k_fast (ORBMI_FAST=v1), 2 alternations
-            v() { tail -1 $OUT/$1.log | python -c 'import json,sys; d=json.load(sys.stdin); print(d["value"], d["stage_ms_per_launch"]["fast"])'; }
-            for i in 1 2; do
-                for sg in 0 1 2; do
-                    ORBMI_FAST_SEG=$sg run fastseg_${sg}_$i 300 python bench.py --full --mode batch --steps 20 --warmup 4 --no-cpu-baseline
-                    echo "seg $sg: $(v fastseg_${sg}_$i)" | tee -a $OUT/fastseg.txt
-                done
-                ORBMI_FAST=v1 run fastseg_v1_$i 300 python bench.py --full --mode batch --steps 20 --warmup 4 --no-cpu-baseline
-                echo "v1: $(v fastseg_v1_$i)" | tee -a $OUT/fastseg.txt
-            done; cp $OUT/fastseg.txt $P/;;
         blurab)
             # config 5 batch: GaussianBlur on a side stream (default) / inside the octree launch / after it
             v() { tail -1 $OUT/$1.log | python -c 'import json,sys; d=json.load(sys.stdin); print(d["value"], d["ms_per_step"])'; }

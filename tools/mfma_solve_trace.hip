@@ -1,5 +1,5 @@
 // Phase timing of k_ba_solve_mfma<T> (LocalBA reduced-system blocked LDL^T on MFMA) on a random
-// SPD 6K x 6K system, against the VALU pivot-wave solve on the same system.
+// SPD 6K x 6K system.
 // Build: hipcc -O3 -std=c++17 -ffp-contract=off --offload-arch=gfx950 -DORBMI_SOLVE_TRACE -Wno-unused-value \
 //        -I include -I orb_slam2_with_comment_amd/csrc tools/mfma_solve_trace.hip -o tools/ubench/mfma_solve_trace
 #include "lba.hip"
@@ -12,7 +12,7 @@ int main(int argc, char** argv) {
     const int np = argc > 1 ? atoi(argv[1]) : 20, N = 6 * np, T = (N + 15) / 16;
     std::mt19937 rng(1);
     std::uniform_real_distribution<double> U(-1, 1);
-    std::vector<double> M(N * N), A(N * N, 0.0), b(N), packedS(kBaPacked, 0.0);
+    std::vector<double> M(N * N), A(N * N, 0.0), b(N);
     for (auto& v : M) v = U(rng);
     for (int i = 0; i < N; i++)
         for (int j = 0; j < N; j++) {
@@ -21,15 +21,10 @@ int main(int argc, char** argv) {
             A[i * N + j] = s + (i == j ? N : 0);
         }
     for (auto& v : b) v = U(rng);
-    for (int r = 0; r < N; r++)
-        for (int c = r; c < N; c++) packedS[r * N - r * (r - 1) / 2 + (c - r)] = A[r * N + c];
     double *dS, *dbs, *dxp;
     int* dist;
     hipMalloc(&dS, kBaPacked * 8); hipMalloc(&dbs, kBaMaxN * 8); hipMalloc(&dxp, kBaMaxN * 8); hipMalloc(&dist, 16);
-    const bool pipe = getenv("PIPE") != nullptr;
-    if (pipe) {
-        hipMemcpy(dS, packedS.data(), kBaPacked * 8, hipMemcpyHostToDevice);
-    } else {  // k_ba_schur's tile layout (both triangles of the diagonal tiles, right-hand side column)
+    {   // k_ba_schur's tile layout (both triangles of the diagonal tiles, right-hand side column)
         std::vector<double> tiles(kBaPacked, 0.0);
         for (int r = 0; r < N; r++) {
             for (int c = r; c < N; c++) {
@@ -58,7 +53,6 @@ int main(int argc, char** argv) {
     hipEvent_t e0, e1;
     hipEventCreate(&e0); hipEventCreate(&e1);
     auto launch = [&] {
-        if (pipe) { hipLaunchKernelGGL(k_ba_solve_pipe, dim3(1), dim3(kBaSolvePipeThreads), 0, 0, a); return; }
         switch (T) {
             case 1: hipLaunchKernelGGL(k_ba_solve_mfma<1>, dim3(1), dim3(kBaMfmaThreads), 0, 0, a); break;
             case 2: hipLaunchKernelGGL(k_ba_solve_mfma<2>, dim3(1), dim3(kBaMfmaThreads), 0, 0, a); break;
@@ -88,8 +82,7 @@ int main(int argc, char** argv) {
         for (int j = 0; j < N; j++) s += A[i * N + j] * x[j];
         res = std::max(res, std::fabs(s - b[i]));
     }
-    printf("%s np=%d N=%d T=%d  avg kernel %.2f us  residual %.3e\n", pipe ? "pipe" : "mfma", np, N, T, ms * 1e3 / reps, res);
-    if (pipe) return 0;
+    printf("mfma np=%d N=%d T=%d  avg kernel %.2f us  residual %.3e\n", np, N, T, ms * 1e3 / reps, res);
     auto cy = [&](int i, int j) { return (long long)(tr[j] - tr[i]); };
     // factor wave: 8p (A_pp final, factor starts), 8p+1 (E_p published); tile wave 0: 8p+2 (E_p
     // seen), 8p+3 (its row panel done), 8p+4 (every row panel done), 8p+5 (its updates done)
