@@ -1293,7 +1293,7 @@ int orbmi_search_by_projection_sim3(orbmi_matcher* h, const orbmi_frame_view* kf
             unsigned long long best = ~0ull;
             ORBMI_HIP(hipMemcpyAsync(&best, a.best + i, sizeof(best), hipMemcpyDeviceToHost, m.ls()));
             ORBMI_HIP(hipStreamSynchronize(m.ls()));
-            if (best != ~0ull && (int)(best >> 40) <= 50) idx = (int)(best & 0xFFFFF);  // TH_LOW
+            if (best != ~0ull && (int)(best >> 40) <= orbmi::TH_LOW) idx = (int)(best & 0xFFFFF);
         }
         if (idx < 0) continue;
         matched[idx] = i;

@@ -6,6 +6,8 @@
 
 namespace orbmi {
 
+constexpr int TH_HIGH = 100, TH_LOW = 50;  // ORBmatcher's descriptor-distance thresholds (src/ORBmatcher.cc:37-38)
+
 // Frame view resolved to device pointers; pose and scale tables travel by value.
 struct DevFrame {
     int n;                 // capacity when n_dev is set

@@ -4,8 +4,23 @@
 //   k_candidates<G>     SearchByProjection(F, MPs) / (CF, LF): window + static filters + Hamming,
 //                       G lanes per query (map point / LF keypoint), sorted top-8 prefix
 //   k_greedy            exact greedy replay of the order-dependent exclusion           one workgroup
+//   k_track_update      Tracking's pass over mvpMapPoints after a PoseOptimization     one workgroup
 //   k_bow_*             SearchByBoW: node merge-join + per-node greedy (one wave / node)
 //   k_xmatch_*          cross-stream brute-force matching of config 4 (build-defined)
+//   k_tri_*             SearchForTriangulation of several (KF1, KF2) pairs, histogram per pair
+//   k_triangulate[_par] CreateNewMapPoints' triangulation of the matches       thread / (keypoint, pair)
+//   k_fuse[_multi]      Fuse(KF, MPs): the search, 8 lanes per point, one or several keyframes
+//   k_grid_build_multi  the grids of a batched Fuse's keyframes                  workgroup / keyframe
+//   k_sim3_grids / _search / _agree   SearchBySim3: both grids, both directions, the agreement
+//   k_proj_sim3         SearchByProjection(KF, Scw): candidate lists for the host's replay
+//   k_patch_desc        recomputed descriptors into map-point records
+//   k_distinctive       MapPoint::ComputeDistinctiveDescriptors                       one wave / point
+//
+// One window walk (for_features_in_area<G>) serves all seven projection-guided searches: the
+// tracking pair and their greedy fallback through window_candidates; Fuse, both directions of
+// SearchBySim3 and SearchByProjection(KF, Scw) through the keyframe query (kf_project ...
+// windowed_best; k_sim3_search writes two of its steps out, see there).  frustum_record and
+// lf_query keep Frame.cc's own projection (see there).
 //
 // Candidate order.  GetFeaturesInArea visits cells ix-major, iy-minor, keypoints in index
 // order inside a cell, so the reference's candidate order is the lexicographic order of
@@ -31,8 +46,7 @@
 namespace orbmi {
 
 constexpr int kGridCols = 64, kGridRows = 48, kGridCells = kGridCols * kGridRows;
-constexpr int TH_HIGH = 100, TH_LOW = 50, HISTO_LENGTH = 30;
-
+constexpr int HISTO_LENGTH = 30;
 
 __device__ inline int popc_desc(const uint8_t* a, const uint8_t* b) {
     const uint4* x = reinterpret_cast<const uint4*>(a);
@@ -86,9 +100,11 @@ __global__ __launch_bounds__(1024) void k_grid_build_multi(const FuseKF* __restr
     grid_build_block(K.F, const_cast<int*>(K.cs), const_cast<int*>(K.cl), kp_cell + (size_t)blockIdx.x * ncap);
 }
 
-// Frame::GetFeaturesInArea (src/Frame.cc:353-410): calls fn(idx) for every keypoint in the
-// window passing the level filter, in arbitrary order.
-template <int G = 1, class Fn>
+// Frame::GetFeaturesInArea (src/Frame.cc:353-410), the one walk of every projection-guided
+// search: calls fn(idx, cell) for every keypoint in the window passing the level filter.  The G
+// lanes of a group share out the window's cells (cell ci on lane ci mod G); G = 1 visits them in
+// the reference's order.
+template <int G, class Fn>
 __device__ inline void for_features_in_area(const DevFrame& F, const int* cell_start, const int* cell_list,
                                             float x, float y, float r, int minLevel, int maxLevel, int glane, Fn fn) {
     const int nMinCellX = max(0, (int)floorf((x - F.min_x - r) * F.grid_w_inv));
@@ -115,14 +131,31 @@ __device__ inline void for_features_in_area(const DevFrame& F, const int* cell_s
         }
     }
 }
-template <class Fn>
-__device__ inline void for_features_in_area(const DevFrame& F, const int* cell_start, const int* cell_list,
-                                            float x, float y, float r, int minLevel, int maxLevel, Fn fn) {
-    for_features_in_area<1>(F, cell_start, cell_list, x, y, r, minLevel, maxLevel, 0, fn);
-}
 
 __device__ inline unsigned long long cand_entry(int dist, int cell, int idx) {
     return ((unsigned long long)dist << 40) | ((unsigned long long)cell << 20) | (unsigned)idx;
+}
+
+// A tracking search's window: centre, radius (also the bound on the right-image coordinate ur),
+// GetFeaturesInArea's level limits and the query's descriptor
+struct Window {
+    float x, y, r, ur;
+    int minL, maxL;
+    const uint8_t* desc;
+};
+
+// SearchByProjection's static part on a window (:88-123, :1594-1625): emit(key) for every keypoint
+// that also passes the stereo test; the query's descriptor is loaded once, ahead of the walk
+template <int G, class Emit>
+__device__ inline void window_candidates(const DevFrame& F, const int* cs, const int* cl, const Window& w, int glane,
+                                         Emit emit) {
+    const uint4* md = reinterpret_cast<const uint4*>(w.desc);
+    const uint4 m0 = md[0], m1 = md[1];
+    for_features_in_area<G>(F, cs, cl, w.x, w.y, w.r, w.minL, w.maxL, glane, [&](int idx, int cell) {
+        if (F.u_right && F.u_right[idx] > 0 && fabsf(w.ur - F.u_right[idx]) > w.r) return;
+        const uint4* fd = reinterpret_cast<const uint4*>(F.desc + 32 * (long long)idx);
+        emit(cand_entry(popc256(m0, m1, fd[0], fd[1]), cell, idx));
+    });
 }
 
 // R*p + t, float, left to right (pinned P10: cv::gemm small-matrix path)
@@ -135,10 +168,77 @@ __device__ inline void camera_center(const float* T, float* o) {
     for (int c = 0; c < 3; c++) o[c] = -((T[c] * T[3] + T[4 + c] * T[7]) + T[8 + c] * T[11]);
 }
 
+// -------------------------------------------------------------------------- keyframe query
+// How a map point becomes a window in a keyframe: the steps that Fuse, SearchBySim3 and
+// SearchByProjection(KF, Scw) share, each in the one operation order of all three.  The validity
+// flags, the vector the distance is taken from, the gates on a keypoint and the outputs stay with
+// the callers.
+
+// the pinhole projection of Pc (intrinsics passed in: SearchBySim3 projects with KF1's) and
+// KeyFrame::IsInImage of F
+__device__ inline bool kf_project(const DevFrame& F, float fx, float fy, float cx, float cy, const float* Pc, float* u,
+                                  float* v, float* invz) {
+    *invz = 1.0f / Pc[2];
+    const float x = Pc[0] * *invz, y = Pc[1] * *invz;
+    *u = fx * x + cx;
+    *v = fy * y + cy;
+    return *u >= F.min_x && *u < F.max_x && *v >= F.min_y && *v < F.max_y;
+}
+
+// dist inside the point's scale-invariance range [0.8 mfMinDistance, 1.2 mfMaxDistance]
+__device__ inline bool in_distance_range(const orbmi_mappoint& mp, float dist) {
+    const float maxDistance = 1.2f * mp.max_distance, minDistance = 0.8f * mp.min_distance;
+    return !(dist < minDistance || dist > maxDistance);
+}
+
+// the point is seen within 60 degrees of its mean viewing direction: PO . Pn >= 0.5 dist
+__device__ inline bool in_viewing_cone(const orbmi_mappoint& mp, const float* PO, float dist) {
+    const double dot = (double)PO[0] * mp.normal[0] + (double)PO[1] * mp.normal[1] + (double)PO[2] * mp.normal[2];
+    return !(dot < 0.5 * (double)dist);
+}
+
+// MapPoint::PredictScale(dist, .) against F's pyramid
+__device__ inline int predict_level(const DevFrame& F, float max_distance, float dist) {
+    const float ratio = max_distance / dist;
+    int nScale = (int)ceilf((float)log((double)ratio) / F.log_scale_factor);
+    if (nScale < 0) nScale = 0;
+    else if (nScale >= F.nlevels) nScale = F.nlevels - 1;
+    return nScale;
+}
+
+// The least key (cand_entry: the best distance, ties to the first keypoint of the reference's grid
+// order) over F's keypoints inside the window of radius th * scale[level] around (u, v), level
+// predicted from dist, at octaves [level - 1, level] (GetFeaturesInArea without level limits, then
+// the octave test, as the reference has it), that pass keep(idx, kp); seen(distance, key) is told
+// every key.  The G lanes of a group share the window's cells and every lane returns the group's
+// minimum; a group with ok = false only takes part in that minimum.
+template <int G, class Keep, class Seen>
+__device__ inline unsigned long long windowed_best(const DevFrame& F, const int* cs, const int* cl,
+                                                   const orbmi_mappoint& mp, bool ok, float u, float v, float dist,
+                                                   float th, int glane, Keep keep, Seen seen) {
+    unsigned long long best = ~0ull;
+    if (ok) {
+        const int level = predict_level(F, mp.max_distance, dist);
+        const float radius = th * F.scale[level];
+        for_features_in_area<G>(F, cs, cl, u, v, radius, -1, -1, glane, [&](int idx, int cell) {
+            const orbmi_keypoint kp = F.keys[idx];
+            if (kp.octave < level - 1 || kp.octave > level) return;
+            if (!keep(idx, kp)) return;
+            const int d = popc_desc(mp.desc, F.desc + 32 * (long long)idx);
+            const unsigned long long e = cand_entry(d, cell, idx);
+            best = e < best ? e : best;
+            seen(d, e);
+        });
+    }
+    return group_min_u64<G>(best);
+}
+
 // -------------------------------------------------------------------------- frustum
 // Frame::isInFrustum (src/Frame.cc:296-353) of one map point at pose T: its track record.  The
 // standalone kernel and the local-map candidate kernel both run this one sequence of operations
 // (one rounding each, -ffp-contract=off), so their records agree bit for bit.
+// Not the keyframe query above (predict_level apart): Frame.cc rounds fx * x first, tests
+// inclusive bounds and divides for viewCos, and the record keeps those bits.
 __device__ inline orbmi_mappoint_track frustum_record(const DevFrame& F, const Pose34& T, const orbmi_mappoint& mp,
                                                       float viewingCosLimit) {
     orbmi_mappoint_track t = {0, 0.f, 0.f, 0.f, 0, 0.f};
@@ -167,10 +267,7 @@ __device__ inline orbmi_mappoint_track frustum_record(const DevFrame& F, const P
         }
     }
     if (ok) {
-        const float ratio = mp.max_distance / dist;
-        int nScale = (int)ceilf((float)log((double)ratio) / F.log_scale_factor);
-        if (nScale < 0) nScale = 0;
-        else if (nScale >= F.nlevels) nScale = F.nlevels - 1;
+        const int nScale = predict_level(F, mp.max_distance, dist);
         t.in_view = 1;
         t.proj_x = u;
         t.proj_xr = u - F.bf * invz;
@@ -196,41 +293,25 @@ __global__ __launch_bounds__(256) void k_frustum(DevFrame F, const orbmi_mappoin
 // -------------------------------------------------------------------------- candidates
 // SearchByProjection(F, vpMapPoints, th): static part of the per-point search (:66-123).
 __device__ inline bool local_query(const DevFrame& F, const orbmi_mappoint& mp, const orbmi_mappoint_track& t,
-                                   float th, float* x, float* y, float* rs, int* level) {
+                                   float th, Window* w) {
     if (!t.in_view || (mp.flags & ORBMI_MP_BAD)) return false;
     float r = t.view_cos > 0.998 ? 2.5f : 4.0f;  // RadiusByViewingCos (:157-163)
     if (th != 1.0) r *= th;
-    *level = t.level;
-    *rs = r * F.scale[t.level];
-    *x = t.proj_x;
-    *y = t.proj_y;
+    w->x = t.proj_x;
+    w->y = t.proj_y;
+    w->r = r * F.scale[t.level];
+    w->ur = t.proj_xr;
+    w->minL = t.level - 1;
+    w->maxL = t.level;
+    w->desc = mp.desc;
     return true;
 }
 
-template <class Fn>
-__device__ inline void local_candidates(const DevFrame& F, const int* cs, const int* cl, const orbmi_mappoint& mp,
-                                        const orbmi_mappoint_track& t, float th, Fn emit) {
-    float x, y, rs;
-    int level;
-    if (!local_query(F, mp, t, th, &x, &y, &rs, &level)) return;
-    const uint8_t* md = mp.desc;
-    for_features_in_area(F, cs, cl, x, y, rs, level - 1, level, [&](int idx, int cell) {
-        if (F.u_right && F.u_right[idx] > 0) {
-            const float er = fabsf(t.proj_xr - F.u_right[idx]);
-            if (er > rs) return;
-        }
-        emit(cand_entry(popc_desc(md, F.desc + 32 * (long long)idx), cell, idx));
-    });
-}
-
-// SearchByProjection(CF, LF, th, bMono): projection + static part (:1566-1637)
-struct LfQuery {
-    float u, v, radius, ur;
-    int minL, maxL;
-};
-
+// SearchByProjection(CF, LF, th, bMono): projection + static part (:1566-1637).
+// Not the keyframe query's kf_project: here fx * x is rounded before the division by z and the
+// bounds are inclusive (Frame's mnMinX..mnMaxX), and the searches are pinned to those bits.
 __device__ inline bool lf_query(const DevFrame& CF, const float* Tc, const DevFrame& LF, const orbmi_lastframe_point& p, int i,
-                                float th, bool bForward, bool bBackward, LfQuery* q) {
+                                float th, bool bForward, bool bBackward, Window* w) {
     if (!(p.flags & ORBMI_LF_HAS_MP) || (p.flags & ORBMI_LF_OUTLIER)) return false;
     float x3Dc[3];
     transform(Tc, p.pos, x3Dc);
@@ -242,29 +323,17 @@ __device__ inline bool lf_query(const DevFrame& CF, const float* Tc, const DevFr
     if (!(u >= CF.min_x && u <= CF.max_x)) return false;  // also rejects NaN (zc == 0)
     if (!(v >= CF.min_y && v <= CF.max_y)) return false;
     const int nLastOctave = LF.keys[i].octave;
-    q->u = u;
-    q->v = v;
-    q->radius = th * CF.scale[nLastOctave];
-    q->ur = u - CF.bf * invzc;
-    if (bForward) { q->minL = nLastOctave; q->maxL = -1; }
-    else if (bBackward) { q->minL = 0; q->maxL = nLastOctave; }
-    else { q->minL = nLastOctave - 1; q->maxL = nLastOctave + 1; }
+    w->x = u;
+    w->y = v;
+    w->r = th * CF.scale[nLastOctave];
+    w->ur = u - CF.bf * invzc;
+    if (bForward) { w->minL = nLastOctave; w->maxL = -1; }
+    else if (bBackward) { w->minL = 0; w->maxL = nLastOctave; }
+    else { w->minL = nLastOctave - 1; w->maxL = nLastOctave + 1; }
+    w->desc = p.desc;
     return true;
 }
 
-template <class Fn>
-__device__ inline void lf_candidates(const DevFrame& CF, const float* Tc, const DevFrame& LF, const int* cs, const int* cl,
-                                     const orbmi_lastframe_point& p, int i, float th, bool fw, bool bw, Fn emit) {
-    LfQuery q;
-    if (!lf_query(CF, Tc, LF, p, i, th, fw, bw, &q)) return;
-    for_features_in_area(CF, cs, cl, q.u, q.v, q.radius, q.minL, q.maxL, [&](int i2, int cell) {
-        if (CF.u_right && CF.u_right[i2] > 0) {
-            const float er = fabsf(q.ur - CF.u_right[i2]);
-            if (er > q.radius) return;
-        }
-        emit(cand_entry(popc_desc(p.desc, CF.desc + 32 * (long long)i2), cell, i2));
-    });
-}
 
 __device__ inline void motion_direction(const DevFrame& CF, const float* Tc, const DevFrame& LF, int mono, bool* fw,
                                         bool* bw) {
@@ -307,31 +376,10 @@ struct CandArgs {
     int gate_min;
 };
 
-struct Window {
-    float x, y, r, ur;
-    int minL, maxL;
-    const uint8_t* desc;
-};
-
-__device__ inline bool local_window(const CandArgs& a, const orbmi_mappoint& mp, const orbmi_mappoint_track& t,
-                                    Window* w) {
-    int level;
-    if (!local_query(a.F, mp, t, a.th, &w->x, &w->y, &w->r, &level)) return false;
-    w->minL = level - 1;
-    w->maxL = level;
-    w->ur = t.proj_xr;
-    w->desc = mp.desc;
-    return true;
-}
-
+// query q's window: the mode switch
 __device__ inline bool make_window(const CandArgs& a, int q, const float* Tc, bool fw, bool bw, Window* w) {
-    if (a.mode == 0) return local_window(a, a.mps[q], a.tr[q], w);
-    const orbmi_lastframe_point& p = a.lfp[q];
-    LfQuery lq;
-    if (!lf_query(a.F, Tc, a.LF, p, q, a.th, fw, bw, &lq)) return false;
-    w->x = lq.u; w->y = lq.v; w->r = lq.radius; w->ur = lq.ur; w->minL = lq.minL; w->maxL = lq.maxL;
-    w->desc = p.desc;
-    return true;
+    if (a.mode == 0) return local_query(a.F, a.mps[q], a.tr[q], a.th, w);
+    return lf_query(a.F, Tc, a.LF, a.lfp[q], q, a.th, fw, bw, w);
 }
 
 // FR (mode 0 only): the group first computes its point's isInFrustum record (every lane the same
@@ -362,7 +410,7 @@ __global__ __launch_bounds__(256) void k_candidates(CandArgs a) {
                 a.tr_out[q] = t;
                 if (t.in_view && a.n_in_view) atomicAdd(a.n_in_view, 1);
             }
-            valid = local_window(a, mp, t, &w);
+            valid = local_query(a.F, mp, t, a.th, &w);
         }
     } else {
         valid = q < nq && make_window(a, q, Tc.m, fw, bw, &w);
@@ -370,35 +418,11 @@ __global__ __launch_bounds__(256) void k_candidates(CandArgs a) {
     if (lane == 0) cnt[gl] = 0;
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
-    if (valid) {
-        const DevFrame& F = a.F;
-        const int nMinCellX = max(0, (int)floorf((w.x - F.min_x - w.r) * F.grid_w_inv));
-        const int nMaxCellX = min(kGridCols - 1, (int)ceilf((w.x - F.min_x + w.r) * F.grid_w_inv));
-        const int nMinCellY = max(0, (int)floorf((w.y - F.min_y - w.r) * F.grid_h_inv));
-        const int nMaxCellY = min(kGridRows - 1, (int)ceilf((w.y - F.min_y + w.r) * F.grid_h_inv));
-        if (nMinCellX < kGridCols && nMaxCellX >= 0 && nMinCellY < kGridRows && nMaxCellY >= 0) {
-            const int ny = nMaxCellY - nMinCellY + 1, ncell = (nMaxCellX - nMinCellX + 1) * ny;
-            const bool bCheckLevels = (w.minL > 0) || (w.maxL >= 0);
-            const uint4* md = reinterpret_cast<const uint4*>(w.desc);
-            const uint4 m0 = md[0], m1 = md[1];
-            for (int ci = lane; ci < ncell; ci += G) {
-                const int c = (nMinCellX + ci / ny) * kGridRows + nMinCellY + ci % ny;
-                for (int j = a.cs[c]; j < a.cs[c + 1]; j++) {
-                    const int idx = a.cl[j];
-                    const orbmi_keypoint kp = F.keys[idx];
-                    if (bCheckLevels) {
-                        if (kp.octave < w.minL) continue;
-                        if (w.maxL >= 0 && kp.octave > w.maxL) continue;
-                    }
-                    if (!(fabsf(kp.x - w.x) < w.r && fabsf(kp.y - w.y) < w.r)) continue;
-                    if (F.u_right && F.u_right[idx] > 0 && fabsf(w.ur - F.u_right[idx]) > w.r) continue;
-                    const uint4* fd = reinterpret_cast<const uint4*>(F.desc + 32 * (long long)idx);
-                    const int pos = atomicAdd(&cnt[gl], 1);
-                    if (pos < cap) buf[gl][pos] = cand_entry(popc256(m0, m1, fd[0], fd[1]), c, idx);
-                }
-            }
-        }
-    }
+    if (valid)
+        window_candidates<G>(a.F, a.cs, a.cl, w, lane, [&](unsigned long long e) {
+            const int pos = atomicAdd(&cnt[gl], 1);
+            if (pos < cap) buf[gl][pos] = e;
+        });
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
@@ -411,19 +435,7 @@ __global__ __launch_bounds__(256) void k_candidates(CandArgs a) {
             const unsigned long long e = buf[gl][p];
             if ((k == 0 || e > last) && e < m) m = e;
         }
-        if constexpr (G == 16) {  // group = one DPP row: four DPP moves, no LDS permute round trips
-            unsigned long long v;
-            v = dpp_mov_u64<kDppXor1>(m); m = v < m ? v : m;
-            v = dpp_mov_u64<kDppXor2>(m); m = v < m ? v : m;
-            v = dpp_mov_u64<kDppHalfMirror>(m); m = v < m ? v : m;
-            v = dpp_mov_u64<kDppRor8>(m); m = v < m ? v : m;
-        } else {
-#pragma unroll
-            for (int o = G / 2; o > 0; o >>= 1) {
-                const unsigned long long v = __shfl_xor(m, o, G);
-                m = v < m ? v : m;
-            }
-        }
+        m = group_min_u64<G>(m);
         if (valid && lane == 0) a.top[(long long)q * kTopK + k] = m;
         last = m;
     }
@@ -488,10 +500,15 @@ __device__ inline int greedy_eval(const GreedyArgs& a, int q, const float* Tc, b
                 for (int j = 0; j < 16; j++)
                     if (e[j] != ~0ull) take(e[j]);
             }
-        } else if (a.mode == 0) {  // overflowed list: enumerate again
-            local_candidates(a.F, a.cs, a.cl, a.mps[q], a.tr[q], a.th, take);
-        } else {
-            lf_candidates(a.F, Tc, a.LF, a.cs, a.cl, a.lfp[q], q, a.th, fw, bw, take);
+        } else {  // overflowed list: enumerate again (the walk with G = 1)
+            // (a call per mode, as before: the compiler keeps the two walks apart, and k_greedy's
+            // opcode counts stay comparable under tools/asm_kernel_diff.py --ops)
+            Window w;
+            if (a.mode == 0) {
+                if (local_query(a.F, a.mps[q], a.tr[q], a.th, &w)) window_candidates<1>(a.F, a.cs, a.cl, w, 0, take);
+            } else if (lf_query(a.F, Tc, a.LF, a.lfp[q], q, a.th, fw, bw, &w)) {
+                window_candidates<1>(a.F, a.cs, a.cl, w, 0, take);
+            }
         }
     }
     if (b1 == ~0ull) return -1;
@@ -1840,22 +1857,10 @@ int launch_create_points(Matcher& m, const DevFrame& KF1, const uint8_t* has1, c
 // the reference's grid order wins ties (key dist << 40 | cell << 20 | idx).  The map updates
 // (Replace / AddObservation) are the caller's sequential replay of (best_idx, best_dist) in
 // list order (include/orbmi.h).
-// minimum over the G lanes of a group (G = 1 or 8, groups aligned inside a DPP row)
-template <int G>
-__device__ inline unsigned long long group_min_u64(unsigned long long v) {
-    if constexpr (G == 8) {
-        unsigned long long w;
-        w = dpp_mov_u64<kDppXor1>(v); v = w < v ? w : v;
-        w = dpp_mov_u64<kDppXor2>(v); v = w < v ? w : v;
-        w = dpp_mov_u64<kDppHalfMirror>(v); v = w < v ? w : v;
-    }
-    return v;
-}
 
-// candidate i of Fuse on G lanes: every lane runs the projection and the tests, the window's
-// grid cells are shared out among the G lanes (cell ci on lane ci mod G), the keys meet in a
-// group minimum; lane 0 of the group writes.  valid = false: the lanes only take part in the
-// group minimum.
+// candidate i of Fuse on G lanes: every lane runs the keyframe query's tests, the group shares
+// the window (windowed_best); lane 0 of the group writes.  valid = false: the lanes only take part
+// in the group minimum.
 template <int G>
 __device__ inline void fuse_one(const DevFrame& F, const int* __restrict__ cs, const int* __restrict__ cl,
                                 const orbmi_mappoint* __restrict__ mps, const uint8_t* __restrict__ in_kf, int i,
@@ -1871,52 +1876,30 @@ __device__ inline void fuse_one(const DevFrame& F, const int* __restrict__ cs, c
         ok = !(Pc[2] < 0.0f);
     }
     float u = 0, v = 0, invz = 0, dist3D = 0;
-    if (ok) {
-        invz = 1.0f / Pc[2];
-        const float x = Pc[0] * invz, y = Pc[1] * invz;
-        u = F.fx * x + F.cx;
-        v = F.fy * y + F.cy;
-        ok = u >= F.min_x && u < F.max_x && v >= F.min_y && v < F.max_y;  // KeyFrame::IsInImage
-    }
+    if (ok) ok = kf_project(F, F.fx, F.fy, F.cx, F.cy, Pc, &u, &v, &invz);
     if (ok) {
         float Ow[3];
         camera_center(T.m, Ow);
-        const float maxDistance = 1.2f * mp.max_distance, minDistance = 0.8f * mp.min_distance;
         const float PO[3] = {mp.pos[0] - Ow[0], mp.pos[1] - Ow[1], mp.pos[2] - Ow[2]};
         dist3D = (float)sqrt((double)PO[0] * PO[0] + (double)PO[1] * PO[1] + (double)PO[2] * PO[2]);
-        ok = !(dist3D < minDistance || dist3D > maxDistance);
-        if (ok) {
-            const double dot = (double)PO[0] * mp.normal[0] + (double)PO[1] * mp.normal[1] + (double)PO[2] * mp.normal[2];
-            ok = !(dot < 0.5 * (double)dist3D);
+        ok = in_distance_range(mp, dist3D) && in_viewing_cone(mp, PO, dist3D);
+    }
+    // the chi2 gates on the reprojection error (:1066-1089)
+    const auto chi2_ok = [&](int idx, const orbmi_keypoint& kp) {
+        const float inv = 1.0f / (F.scale[kp.octave] * F.scale[kp.octave]);  // mvInvLevelSigma2
+        const float ex = u - kp.x, ey = v - kp.y;
+        if (F.u_right && F.u_right[idx] >= 0) {
+            const float er = (u - F.bf * invz) - F.u_right[idx];
+            const float e2 = ex * ex + ey * ey + er * er;
+            if ((double)(e2 * inv) > 7.8) return false;
+        } else {
+            const float e2 = ex * ex + ey * ey;
+            if ((double)(e2 * inv) > 5.99) return false;
         }
-    }
-    unsigned long long best = ~0ull;
-    if (ok) {
-        const float ratio = mp.max_distance / dist3D;  // MapPoint::PredictScale(dist, KeyFrame*)
-        int nPredictedLevel = (int)ceilf((float)log((double)ratio) / F.log_scale_factor);
-        if (nPredictedLevel < 0) nPredictedLevel = 0;
-        else if (nPredictedLevel >= F.nlevels) nPredictedLevel = F.nlevels - 1;
-        const float radius = th * F.scale[nPredictedLevel];
-        const float ur = u - F.bf * invz;
-        for_features_in_area<G>(F, cs, cl, u, v, radius, -1, -1, glane, [&](int idx, int cell) {
-            const orbmi_keypoint kp = F.keys[idx];
-            const int kpLevel = kp.octave;
-            if (kpLevel < nPredictedLevel - 1 || kpLevel > nPredictedLevel) return;
-            const float inv = 1.0f / (F.scale[kpLevel] * F.scale[kpLevel]);  // mvInvLevelSigma2
-            const float ex = u - kp.x, ey = v - kp.y;
-            if (F.u_right && F.u_right[idx] >= 0) {
-                const float er = ur - F.u_right[idx];
-                const float e2 = ex * ex + ey * ey + er * er;
-                if ((double)(e2 * inv) > 7.8) return;
-            } else {
-                const float e2 = ex * ex + ey * ey;
-                if ((double)(e2 * inv) > 5.99) return;
-            }
-            const unsigned long long e = cand_entry(popc_desc(mp.desc, F.desc + 32 * (long long)idx), cell, idx);
-            best = e < best ? e : best;
-        });
-    }
-    best = group_min_u64<G>(best);
+        return true;
+    };
+    const unsigned long long best =
+        windowed_best<G>(F, cs, cl, mp, ok, u, v, dist3D, th, glane, chi2_ok, [](int, unsigned long long) {});
     if (!valid || glane != 0) return;
     if (best != ~0ull) {
         bd = (int)(best >> 40);
@@ -1925,9 +1908,7 @@ __device__ inline void fuse_one(const DevFrame& F, const int* __restrict__ cs, c
     const bool fused = bi >= 0 && bd <= TH_LOW;
     best_idx[i] = fused ? bi : -1;
     best_dist[i] = bi >= 0 ? bd : 256;
-    // one atomic per wave: a counter shared by the whole grid serialises per-thread atomics
-    const unsigned long long m = __ballot(fused);
-    if (ncand && fused && (threadIdx.x & 63) == __ffsll((long long)m) - 1) atomicAdd(ncand, (int)__popcll(m));
+    wave_count_add(ncand, fused);
 }
 
 constexpr int kFuseLanes = 8;  // lanes per candidate map point (a window spans a few grid cells)
@@ -1958,6 +1939,20 @@ int launch_fuse(Matcher& m, const DevFrame& F, const orbmi_mappoint* mps, const 
     return hipGetLastError() == hipSuccess ? ORBMI_OK : ORBMI_E_HIP;
 }
 
+// nk keyframe grids in the matcher's multi-grid buffers, cell_list / kp_cell rows of ncap entries:
+// reserves them and hands grid k's (cell_start, cell_list, kp_cell) to assign
+template <class Assign>
+static int multi_grids(Matcher& m, int nk, int ncap, Assign assign) {
+    int rc;
+    if ((rc = ensure_buf(&m.d_mcell_start, &m.cap_mcell_start, (size_t)(kGridCells + 1) * nk))) return rc;
+    if ((rc = ensure_buf(&m.d_mcell_list, &m.cap_mcell_list, (size_t)ncap * nk))) return rc;
+    if ((rc = ensure_buf(&m.d_mkp_cell, &m.cap_mkp_cell, (size_t)ncap * nk))) return rc;
+    for (int k = 0; k < nk; k++)
+        assign(k, m.d_mcell_start + (size_t)k * (kGridCells + 1), m.d_mcell_list + (size_t)k * ncap,
+               m.d_mkp_cell + (size_t)k * ncap);
+    return ORBMI_OK;
+}
+
 // the keyframes' grids and output rows of a batched Fuse search, filled into the host table
 // (keyframe k's results at best_idx / best_dist + k * n); *ncap_out = the grids' row length
 int fuse_multi_prepare(Matcher& m, int nkf, FuseKF* kfs_host, int n, int* best_idx, int* best_dist, int* ncand,
@@ -1967,20 +1962,15 @@ int fuse_multi_prepare(Matcher& m, int nkf, FuseKF* kfs_host, int n, int* best_i
         if (kfs_host[k].F.n > kGreedyMaxKp) return ORBMI_E_UNSUPPORTED;
         ncap = std::max(ncap, kfs_host[k].F.n);
     }
-    int rc;
-    if ((rc = ensure_buf(&m.d_mcell_start, &m.cap_mcell_start, (size_t)(kGridCells + 1) * nkf))) return rc;
-    if ((rc = ensure_buf(&m.d_mcell_list, &m.cap_mcell_list, (size_t)ncap * nkf))) return rc;
-    if ((rc = ensure_buf(&m.d_mkp_cell, &m.cap_mkp_cell, (size_t)ncap * nkf))) return rc;
-    for (int k = 0; k < nkf; k++) {
+    *ncap_out = ncap;
+    return multi_grids(m, nkf, ncap, [&](int k, int* cs, int* cl, int*) {  // kp_cell: k_grid_build_multi's own
         FuseKF& K = kfs_host[k];
-        K.cs = m.d_mcell_start + (size_t)k * (kGridCells + 1);
-        K.cl = m.d_mcell_list + (size_t)k * ncap;
+        K.cs = cs;
+        K.cl = cl;
         K.best_idx = best_idx + (size_t)k * n;
         K.best_dist = best_dist + (size_t)k * n;
         K.ncand = ncand + k;
-    }
-    *ncap_out = ncap;
-    return ORBMI_OK;
+    });
 }
 
 // kfs_host == nullptr: the caller prepared (fuse_multi_prepare -> ncap) and uploaded the table
@@ -2036,6 +2026,9 @@ __global__ __launch_bounds__(256) void k_sim3_search(const Sim3Side* __restrict_
         transform(S.S, Ps, Pc);
         ok = !(Pc[2] < 0.0f);
     }
+    // kf_project and windowed_best written out, with KF1's intrinsics and no gate on a keypoint:
+    // through the helpers this kernel's scalar-register count changes (54 -> 52; with only
+    // windowed_best, 56), and tools/asm_kernel_diff.py holds every kernel to its descriptor
     float u = 0, v = 0, dist3D = 0;
     if (ok) {
         const float invz = 1.0f / Pc[2];
@@ -2045,20 +2038,16 @@ __global__ __launch_bounds__(256) void k_sim3_search(const Sim3Side* __restrict_
         ok = u >= F.min_x && u < F.max_x && v >= F.min_y && v < F.max_y;  // KeyFrame::IsInImage
     }
     if (ok) {
-        const float maxDistance = 1.2f * mp.max_distance, minDistance = 0.8f * mp.min_distance;
         dist3D = (float)sqrt(((double)Pc[0] * Pc[0] + (double)Pc[1] * Pc[1]) + (double)Pc[2] * Pc[2]);  // cv::norm
-        ok = !(dist3D < minDistance || dist3D > maxDistance);
+        ok = in_distance_range(mp, dist3D);
     }
     unsigned long long best = ~0ull;
     if (ok) {
-        const float ratio = mp.max_distance / dist3D;  // MapPoint::PredictScale(dist, KeyFrame*)
-        int nPredictedLevel = (int)ceilf((float)log((double)ratio) / F.log_scale_factor);
-        if (nPredictedLevel < 0) nPredictedLevel = 0;
-        else if (nPredictedLevel >= F.nlevels) nPredictedLevel = F.nlevels - 1;
-        const float radius = th * F.scale[nPredictedLevel];
+        const int level = predict_level(F, mp.max_distance, dist3D);
+        const float radius = th * F.scale[level];
         for_features_in_area<kFuseLanes>(F, S.cs, S.cl, u, v, radius, -1, -1, glane, [&](int idx, int cell) {
             const int kpLevel = F.keys[idx].octave;
-            if (kpLevel < nPredictedLevel - 1 || kpLevel > nPredictedLevel) return;
+            if (kpLevel < level - 1 || kpLevel > level) return;
             const unsigned long long e = cand_entry(popc_desc(mp.desc, F.desc + 32 * (long long)idx), cell, idx);
             best = e < best ? e : best;
         });
@@ -2078,8 +2067,7 @@ __global__ __launch_bounds__(256) void k_sim3_agree(const int* __restrict__ vn1,
         found = idx2 >= 0 && vn2[idx2] == i1;
         if (found) match12[i1] = idx2;
     }
-    const unsigned long long m = __ballot(found);  // one atomic per wave; an integer sum has no order
-    if (found && (threadIdx.x & 63) == __ffsll((long long)m) - 1) atomicAdd(nfound, (int)__popcll(m));
+    wave_count_add(nfound, found);
 }
 
 // sides_host: F, mps, has, n_src, Tcw, S, intrinsics and vn filled by the caller; the grids are
@@ -2090,14 +2078,12 @@ int launch_search_by_sim3(Matcher& m, Sim3Side* sides_host, Sim3Side* sides_dev,
     if (n1 > kGreedyMaxKp || n2 > kGreedyMaxKp) return ORBMI_E_UNSUPPORTED;
     const int ncap = std::max(std::max(n1, n2), 1);
     int rc;
-    if ((rc = ensure_buf(&m.d_mcell_start, &m.cap_mcell_start, (size_t)(kGridCells + 1) * 2))) return rc;
-    if ((rc = ensure_buf(&m.d_mcell_list, &m.cap_mcell_list, (size_t)ncap * 2))) return rc;
-    if ((rc = ensure_buf(&m.d_mkp_cell, &m.cap_mkp_cell, (size_t)ncap * 2))) return rc;
-    for (int k = 0; k < 2; k++) {
-        sides_host[k].cs = m.d_mcell_start + (size_t)k * (kGridCells + 1);
-        sides_host[k].cl = m.d_mcell_list + (size_t)k * ncap;
-        sides_host[k].kc = m.d_mkp_cell + (size_t)k * ncap;
-    }
+    if ((rc = multi_grids(m, 2, ncap, [&](int k, int* cs, int* cl, int* kc) {
+             sides_host[k].cs = cs;
+             sides_host[k].cl = cl;
+             sides_host[k].kc = kc;
+         })))
+        return rc;
     ORBMI_HIP(m.h2d(sides_dev, sides_host, sizeof(Sim3Side) * 2));
     ORBMI_HIP(hipMemsetAsync(already2, 0, (size_t)std::max(n2, 1), m.ls()));
     hipLaunchKernelGGL(k_sim3_grids, dim3(2), dim3(1024), 0, m.ls(), sides_dev, match12, n1, already2, n2);
@@ -2132,45 +2118,21 @@ __global__ __launch_bounds__(256) void k_proj_sim3(DevFrame F, const int* __rest
         transform(a.T, mp.pos, Pc);
         ok = !(Pc[2] < 0.0f);
     }
-    float u = 0, v = 0, dist3D = 0;
+    float u = 0, v = 0, invz = 0, dist3D = 0;
+    if (ok) ok = kf_project(F, F.fx, F.fy, F.cx, F.cy, Pc, &u, &v, &invz);
     if (ok) {
-        const float invz = 1.0f / Pc[2];
-        const float x = Pc[0] * invz, y = Pc[1] * invz;
-        u = F.fx * x + F.cx;
-        v = F.fy * y + F.cy;
-        ok = u >= F.min_x && u < F.max_x && v >= F.min_y && v < F.max_y;  // KeyFrame::IsInImage
-    }
-    if (ok) {
-        const float maxDistance = 1.2f * mp.max_distance, minDistance = 0.8f * mp.min_distance;
         const float PO[3] = {mp.pos[0] - a.Ow[0], mp.pos[1] - a.Ow[1], mp.pos[2] - a.Ow[2]};
         dist3D = (float)sqrt((double)PO[0] * PO[0] + (double)PO[1] * PO[1] + (double)PO[2] * PO[2]);
-        ok = !(dist3D < minDistance || dist3D > maxDistance);
-        if (ok) {
-            const double dot = (double)PO[0] * mp.normal[0] + (double)PO[1] * mp.normal[1] + (double)PO[2] * mp.normal[2];
-            ok = !(dot < 0.5 * (double)dist3D);
-        }
+        ok = in_distance_range(mp, dist3D) && in_viewing_cone(mp, PO, dist3D);
     }
-    unsigned long long best = ~0ull;
-    if (ok) {
-        const float ratio = mp.max_distance / dist3D;  // MapPoint::PredictScale(dist, KeyFrame*)
-        int nPredictedLevel = (int)ceilf((float)log((double)ratio) / F.log_scale_factor);
-        if (nPredictedLevel < 0) nPredictedLevel = 0;
-        else if (nPredictedLevel >= F.nlevels) nPredictedLevel = F.nlevels - 1;
-        const float radius = a.th * F.scale[nPredictedLevel];
-        for_features_in_area<kFuseLanes>(F, cs, cl, u, v, radius, -1, -1, glane, [&](int idx, int cell) {
-            if (a.occ[idx]) return;
-            const int kpLevel = F.keys[idx].octave;
-            if (kpLevel < nPredictedLevel - 1 || kpLevel > nPredictedLevel) return;
-            const int d = popc_desc(mp.desc, F.desc + 32 * (long long)idx);
-            const unsigned long long e = cand_entry(d, cell, idx);
-            best = e < best ? e : best;
-            if (d <= TH_LOW) {
-                const int pos = atomicAdd(&a.count[i], 1);  // an integer count; the keys order the list
-                if (pos < Matcher::kCandCap) a.list[(size_t)i * Matcher::kCandCap + pos] = e;
-            }
+    const unsigned long long best = windowed_best<kFuseLanes>(
+        F, cs, cl, mp, ok, u, v, dist3D, a.th, glane,
+        [&](int idx, const orbmi_keypoint&) { return !a.occ[idx]; },
+        [&](int d, unsigned long long e) {
+            if (d > TH_LOW) return;
+            const int pos = atomicAdd(&a.count[i], 1);  // an integer count; the keys order the list
+            if (pos < Matcher::kCandCap) a.list[(size_t)i * Matcher::kCandCap + pos] = e;
         });
-    }
-    best = group_min_u64<kFuseLanes>(best);
     if (valid && glane == 0) a.best[i] = best;
 }
 

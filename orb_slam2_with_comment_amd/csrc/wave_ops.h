@@ -1,6 +1,6 @@
 // Wave-level cross-lane primitives for gfx950 (wave64): DPP moves inside a row of 16 lanes and
 // v_permlane16/32_swap across rows, so reductions need no LDS round trip.  Shared by the
-// PoseOptimization and LocalBundleAdjustment kernels; every sum has a fixed order.
+// PoseOptimization, LocalBundleAdjustment and matcher kernels; every sum has a fixed order.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -100,6 +100,35 @@ __device__ inline unsigned long long wave_min_u64_dpp(unsigned long long v) {
     w = swap_partner_u64<16>(v); v = w < v ? w : v;
     w = swap_partner_u64<32>(v); v = w < v ? w : v;
     return v;
+}
+
+// minimum of a u64 key over the G lanes of a group (G a power of two, groups aligned to G lanes;
+// every lane ends with it): G = 1, 8 and 16 stay inside a DPP row, other sizes shuffle
+template <int G>
+__device__ inline unsigned long long group_min_u64(unsigned long long v) {
+    static_assert(G >= 1 && G <= 64 && (G & (G - 1)) == 0, "a power of two up to the wave");
+    if constexpr (G == 8 || G == 16) {
+        unsigned long long w;
+        w = dpp_mov_u64<kDppXor1>(v); v = w < v ? w : v;
+        w = dpp_mov_u64<kDppXor2>(v); v = w < v ? w : v;
+        w = dpp_mov_u64<kDppHalfMirror>(v); v = w < v ? w : v;
+        if constexpr (G == 16) { w = dpp_mov_u64<kDppRor8>(v); v = w < v ? w : v; }
+    } else {
+#pragma unroll
+        for (int o = G / 2; o > 0; o >>= 1) {
+            const unsigned long long w = __shfl_xor(v, o, G);
+            v = w < v ? w : v;
+        }
+    }
+    return v;
+}
+
+// *counter += the number of active lanes with flag set, as one atomic per wave (a counter shared
+// by the whole grid serialises per-thread atomics; an integer sum has no order).  A null counter
+// counts nothing.
+__device__ inline void wave_count_add(int* counter, bool flag) {
+    const unsigned long long m = __ballot(flag);
+    if (counter && flag && (threadIdx.x & 63) == __ffsll((long long)m) - 1) atomicAdd(counter, (int)__popcll(m));
 }
 
 // wave maximum of a u32 key (every lane ends with it), the same exchange pattern

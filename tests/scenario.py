@@ -55,6 +55,75 @@ def lastframe(f, seed=0, outlier=0.05, noobs=0.02, pose_noise=0.0):
     return make_frame(f, pose_noise, seed), lfp
 
 
+BORDERS = ("left", "right", "top", "bottom", "corner")
+
+
+@functools.lru_cache(maxsize=None)
+def border_scene(seed=0):
+    """Search windows that overlap the image borders (the clamped cell ranges of GetFeaturesInArea):
+    a KITTI-shaped keyframe of 200 keypoints, 30 of them (octaves 5-7) along each border as close to
+    it as the 64 x 48 grid still takes them, 8 more in the bottom right corner and 72 inside; and 40
+    map points, 8 per border and 8 at the corner, each built to match one of those keypoints
+    (`slot`): 1.2 scale[octave] pixels further out (inside the chi2 gates of Fuse and inside the
+    image), on the keypoint's predicted level, seen head-on, its descriptor a few bits away.  Every
+    search's radius at these levels (>= 12 px with th >= 5 for Fuse, >= 3 for the local map) reaches
+    past the border.  -> dict(kf, mps, slot, where): where[i] names point i's border."""
+    from orb_slam2_with_comment_amd.types import KP_DTYPE, MAPPOINT_DTYPE, MP_HAS_OBS
+    cam, rng = synth.KITTI, np.random.default_rng(seed)
+    W, H, sf = float(cam.width), float(cam.height), 1.2 ** np.arange(8)
+    # the last column / row of cells ends at 63.5 / 64 of the width and 47.5 / 48 of the height
+    # (AssignFeaturesToGrid rounds): keypoints further out are in no cell
+    x_hi, y_hi = W * 63.5 / 64 - 0.5, H * 47.5 / 48 - 0.5
+    n_side, n_pts = 30, 8
+    groups = {"left": (rng.uniform(1, 5, n_side), rng.uniform(30, H - 30, n_side), (-1, 0)),
+              "right": (rng.uniform(x_hi - 5, x_hi, n_side), rng.uniform(30, H - 30, n_side), (1, 0)),
+              "top": (rng.uniform(30, W - 30, n_side), rng.uniform(1, 5, n_side), (0, -1)),
+              "bottom": (rng.uniform(30, W - 30, n_side), rng.uniform(y_hi - 5, y_hi, n_side), (0, 1)),
+              "corner": (rng.uniform(x_hi - 5, x_hi, n_pts), rng.uniform(y_hi - 5, y_hi, n_pts), (1, 1))}
+    n_in = 200 - 4 * n_side - n_pts
+    keys = np.zeros(200, KP_DTYPE)
+    keys["x"] = np.concatenate([groups[b][0] for b in BORDERS] + [rng.uniform(40, W - 40, n_in)])
+    keys["y"] = np.concatenate([groups[b][1] for b in BORDERS] + [rng.uniform(40, H - 40, n_in)])
+    keys["octave"] = np.concatenate([rng.integers(5, 8, 200 - n_in), rng.integers(0, 8, n_in)])
+    desc = rng.integers(0, 256, (200, 32)).astype(np.uint8)
+    u_right = np.full(200, -1, np.float32)
+    yaw = 0.03
+    Twc = np.eye(4)
+    Twc[:3, :3] = [[np.cos(yaw), 0, np.sin(yaw)], [0, 1, 0], [-np.sin(yaw), 0, np.cos(yaw)]]
+    Twc[:3, 3] = [0.4, -0.1, 2.0]
+    mps, slot, where = np.zeros(5 * n_pts, MAPPOINT_DTYPE), [], []
+    first = 0
+    for b in BORDERS:
+        dx, dy = groups[b][2]
+        for k in range(first, first + n_pts):
+            i, z, step = len(slot), rng.uniform(8, 30), 1.2 * sf[keys["octave"][k]]
+            u = np.clip(keys["x"][k] + dx * step, 0.5, W - 0.5)
+            v = np.clip(keys["y"][k] + dy * step, 0.5, H - 0.5)
+            Xw = Twc[:3, :3] @ (z * np.array([(u - cam.cx) / cam.fx, (v - cam.cy) / cam.fy, 1.0])) + Twc[:3, 3]
+            PO = Xw - Twc[:3, 3]
+            mps["pos"][i], mps["normal"][i] = Xw, PO / np.linalg.norm(PO)
+            mps["max_distance"][i] = np.linalg.norm(PO) * 1.2 ** (int(keys["octave"][k]) - 0.5)
+            mps["min_distance"][i] = mps["max_distance"][i] / 1.2 ** 7
+            d = desc[k].copy()
+            for bit in rng.choice(256, int(rng.integers(0, 10)), replace=False):
+                d[bit >> 3] ^= np.uint8(1 << (bit & 7))
+            mps["desc"][i], mps["flags"][i] = d, MP_HAS_OBS
+            if keys["x"][k] - cam.bf / z > 0:  # the keypoint's own stereo match, where the baseline leaves one
+                u_right[k] = keys["x"][k] - cam.bf / z
+            slot.append(k)
+            where.append(b)
+        first += len(groups[b][0])
+    kf = Frame(keys, desc, u_right, SM.tcw_from_twc(Twc), cam)
+    return {"kf": kf, "mps": mps, "slot": np.array(slot), "where": np.array(where)}
+
+
+def assert_every_border_matched(sc, hit):
+    """hit[i]: the reference matched point i of border_scene to its keypoint.  At least one per
+    border and at the corner, or the scene does not test the clamped windows."""
+    for b in BORDERS:
+        assert np.asarray(hit)[sc["where"] == b].any(), b
+
+
 def bow(frame_kf, frame_f):
     kl, dl, u, d, T = frame_data(frame_kf)
     kf = make_frame(frame_kf)

@@ -3,9 +3,9 @@ sequential CPU restatement, bit-exact on every output index and match count."""
 import numpy as np
 import pytest
 
-from orb_slam2_with_comment_amd.types import MP_HAS_OBS
+from orb_slam2_with_comment_amd.types import LF_HAS_MP, LFPOINT_DTYPE, MP_HAS_OBS, Frame
 
-from scenario import bow, lastframe, local_map, make_frame
+from scenario import assert_every_border_matched, border_scene, bow, lastframe, local_map, make_frame
 
 pytestmark = pytest.mark.gpu
 
@@ -25,15 +25,27 @@ def test_is_in_frustum_parity(oracle, M):
     np.testing.assert_array_equal(t.view(np.uint8), t_ref.view(np.uint8))
 
 
-@pytest.mark.parametrize("th,nnratio,dup", [(1.0, 0.8, 1), (3.0, 0.8, 1), (5.0, 0.6, 1), (1.0, 0.8, 3)])
+@pytest.mark.parametrize("th,nnratio,dup", [(1.0, 0.8, 1), (3.0, 0.8, 1), (5.0, 0.6, 1), (1.0, 0.8, 3),
+                                            (3.0, 0.8, "border")])
 def test_local_search_parity(oracle, M, th, nnratio, dup):
-    F = make_frame(3)
-    mps = local_map((0, 1, 2), seed=int(th * 10) + dup, dup=dup)
+    """dup = "border": scenario.border_scene in place of the local map, whose windows overlap the
+    four image borders and a corner (the oracle matches a point at each)."""
+    if dup == "border":
+        sc = border_scene()
+        F, mps = sc["kf"], sc["mps"]
+        occ = np.zeros(len(F.keys), np.uint8)
+    else:
+        F = make_frame(3)
+        mps = local_map((0, 1, 2), seed=int(th * 10) + dup, dup=dup)
+        occ = (np.random.default_rng(5).random(len(F.keys)) < 0.1).astype(np.uint8)
     tr = oracle.is_in_frustum(F, mps, 0.5)
-    occ = (np.random.default_rng(5).random(len(F.keys)) < 0.1).astype(np.uint8)
     m_ref, n_ref = oracle.search_by_projection_local(F, occ, mps, tr, th, nnratio)
     m, n = M(nnratio).SearchByProjection(F, occ, mps, tr, th)
-    assert n == n_ref and n > 100
+    if dup == "border":
+        assert n == n_ref
+        assert_every_border_matched(sc, m_ref[sc["slot"]] == np.arange(len(mps)))
+    else:
+        assert n == n_ref and n > 100
     np.testing.assert_array_equal(m, m_ref)
 
 
@@ -65,8 +77,11 @@ def test_search_local_points_fused(oracle, M):
     np.testing.assert_array_equal(m, m_ref)
 
 
-@pytest.mark.parametrize("case", ["forward", "backward", "still", "mono", "no_ori", "th14"])
+@pytest.mark.parametrize("case", ["forward", "backward", "still", "mono", "no_ori", "th14", "border"])
 def test_lastframe_parity(oracle, M, case):
+    """border: scenario.border_scene, the last frame holding the points' own keypoints at the current
+    frame's pose, so that every window overlaps a border or the corner (the oracle matches a point
+    at each)."""
     cf = make_frame(3, pose_noise=0.01, seed=1)
     lf, lfp = lastframe(2, seed=4)
     th, mono, ori = 7.0, False, True
@@ -83,10 +98,21 @@ def test_lastframe_parity(oracle, M, case):
     elif case == "th14":
         th = 14.0
     occ = (np.random.default_rng(11).random(len(cf.keys)) < 0.05).astype(np.uint8)
+    if case == "border":
+        sc = border_scene()
+        cf, mps, slot = sc["kf"], sc["mps"], sc["slot"]
+        lf = Frame(cf.keys[slot], cf.desc[slot], cf.u_right[slot], cf.tcw, cf.cam)
+        lfp = np.zeros(len(mps), LFPOINT_DTYPE)
+        lfp["pos"], lfp["desc"], lfp["flags"] = mps["pos"], mps["desc"], LF_HAS_MP | MP_HAS_OBS
+        occ = np.zeros(len(cf.keys), np.uint8)
     m_ref, n_ref = oracle.search_by_projection_last_frame(cf, occ, lf, lfp, th, mono, ori)
     mt = M(0.9, ori)
     m, n = mt.SearchByProjectionLastFrame(cf, occ, lf, lfp, th, mono)
-    assert n == n_ref and n > 50
+    if case == "border":
+        assert n == n_ref
+        assert_every_border_matched(sc, m_ref[slot] == np.arange(len(mps)))
+    else:
+        assert n == n_ref and n > 50
     np.testing.assert_array_equal(m, m_ref)
 
 

@@ -195,9 +195,23 @@ def matcher():
 _SEARCH_REF = {}
 
 
+def _border_search_scene():
+    """scenario.border_scene as both keyframes of SearchBySim3 (one pose, t12 a few millimetres),
+    its points in their keypoints' slots: both directions search windows that overlap the borders."""
+    from scenario import border_scene
+    from orb_slam2_with_comment_amd.types import MAPPOINT_DTYPE
+    b = border_scene()
+    kf, n = b["kf"], len(b["kf"].keys)
+    mps, has = np.zeros(n, MAPPOINT_DTYPE), np.zeros(n, np.uint8)
+    mps[b["slot"]], has[b["slot"]] = b["mps"], 1
+    return {"kf1": kf, "mps1": mps, "has1": has, "kf2": kf, "mps2": mps, "has2": has, "s12": 1.0,
+            "R12": np.eye(3, dtype=np.float32), "t12": np.array([0.002, -0.002, 0.002], np.float32), "th": 7.5,
+            "match12": np.full(n, -1, np.int32)}
+
+
 def _search_ref(f2, s12):
     if (f2, s12) not in _SEARCH_REF:
-        sc = R.sim3_search_scene(4, f2, s12)
+        sc = _border_search_scene() if f2 == "border" else R.sim3_search_scene(4, f2, s12)
         _SEARCH_REF[f2, s12] = (sc, R.search_by_sim3(sc["kf1"], sc["mps1"], sc["has1"], sc["kf2"], sc["mps2"], sc["has2"],
                                                      sc["s12"], sc["R12"], sc["t12"], sc["th"], sc["match12"]))
     return _SEARCH_REF[f2, s12]
@@ -208,16 +222,24 @@ def _gpu_search(matcher, sc, kf2=None):
                                 sc["s12"], sc["R12"], sc["t12"], sc["th"])
 
 
-@pytest.mark.parametrize("f2,s12", [(6, 1.0), (5, 1.0), (6, 1.1)])
+@pytest.mark.parametrize("f2,s12", [(6, 1.0), (5, 1.0), (6, 1.1), ("border", 1.0)])
 def test_search_by_sim3_matches_restatement(oracle, matcher, f2, s12):
     """orbmi_search_by_sim3 on keyframes 4 and 6 / 5 (and with s12 = 1.1, KF2's map scaled to
-    match): vnMatch1, vnMatch2, match12 and nFound exactly the restatement's."""
+    match): vnMatch1, vnMatch2, match12 and nFound exactly the restatement's.  f2 = "border": the
+    windows of both directions overlap the four image borders and a corner (the restatement finds
+    a point at each)."""
     sc, (vn1, vn2, m12, nfound, _) = _search_ref(f2, s12)
     g12, gn, g1, g2 = _gpu_search(matcher, sc)
     np.testing.assert_array_equal(g1, vn1)
     np.testing.assert_array_equal(g2, vn2)
     np.testing.assert_array_equal(g12, m12)
-    assert gn == nfound >= 100
+    if f2 == "border":
+        from scenario import assert_every_border_matched, border_scene
+        b = border_scene()
+        assert gn == nfound
+        assert_every_border_matched(b, m12[b["slot"]] == b["slot"])
+    else:
+        assert gn == nfound >= 100
 
 
 def test_search_by_sim3_projects_with_kf1_intrinsics(oracle, matcher):

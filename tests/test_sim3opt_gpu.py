@@ -116,12 +116,26 @@ def _search(matcher, sc):
     return matcher.SearchByProjectionSim3(sc["kf"], sc["Scw"], sc["mps"], sc["matched"], sc["th"])
 
 
-@pytest.mark.parametrize("seed,s", [(0, 1.3), (1, 1.0), (2, 0.7)])
+@pytest.mark.parametrize("seed,s", [(0, 1.3), (1, 1.0), (2, 0.7), ("border", 1.3)])
 def test_search_by_projection_sim3_matches_restatement(matcher, seed, s):
     """The synthetic keyframe scene: two points competing for one keypoint (the earlier one wins
     although the later one is closer), a point already in `matched`, keypoints occupied on entry, a
     point behind the camera, outside its distance range, with a failing normal, flagged bad,
-    outside the image: `matched` and nmatches exactly the restatement's."""
+    outside the image: `matched` and nmatches exactly the restatement's.  seed = "border":
+    scenario.border_scene under its keyframe's pose times s, whose windows overlap the four image
+    borders and a corner (the restatement matches a point at each)."""
+    if seed == "border":
+        from scenario import assert_every_border_matched, border_scene
+        b = border_scene()
+        kf = b["kf"]
+        Scw = (kf.tcw[:3] * np.float32(s)).astype(np.float32)
+        matched = np.full(len(kf.keys), -1, np.int32)
+        m_ref, n_ref = ref.search_by_projection_sim3(kf, Scw, b["mps"], matched, 10)
+        m, n = matcher.SearchByProjectionSim3(kf, Scw, b["mps"], matched, 10)
+        np.testing.assert_array_equal(m, m_ref)
+        assert n == n_ref
+        assert_every_border_matched(b, m_ref[b["slot"]] == np.arange(len(b["mps"])))
+        return
     sc = ref.projection_scene(seed, s=s)
     why = {}
     m_ref, n_ref = ref.search_by_projection_sim3(sc["kf"], sc["Scw"], sc["mps"], sc["matched"], sc["th"], why)

@@ -2,14 +2,17 @@
 
     hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fno-fast-math \
         --cuda-device-only -S -o old.s csrc/lba.hip      (the same for the new tree -> new.s)
-    python tools/asm_kernel_diff.py old.s new.s [--rename OLD_SYMBOL=NEW_SYMBOL ...] [--show SYMBOL]
+    python tools/asm_kernel_diff.py old.s new.s [--rename OLD_SYMBOL=NEW_SYMBOL ...] [--show SYMBOL] [--ops]
 
 Per kernel of old.s: `same` when the instruction stream between its label and .Lfunc_end and its
 .amdhsa_ descriptor (registers, LDS, scratch) are equal in new.s, `DIFF` with the number of
 differing lines otherwise, `gone` when new.s has no such kernel.  Comments are dropped and the
 function number in .LBB<fn>_<block> labels is normalised.  Exit status 1 on any DIFF.
+--ops adds, per DIFF kernel, the opcodes whose counts differ (s_nop and s_waitcnt apart) and
+whether any of them is floating-point: a reordering of the same opcodes shows none.
 """
 import argparse
+import collections
 import difflib
 import re
 import sys
@@ -51,6 +54,7 @@ def main(argv):
     ap.add_argument("new")
     ap.add_argument("--rename", action="append", default=[], metavar="OLD=NEW")
     ap.add_argument("--show", metavar="SYMBOL", help="print this kernel's differing lines")
+    ap.add_argument("--ops", action="store_true", help="per DIFF kernel: the opcodes whose counts differ")
     opt = ap.parse_args(argv)
     rename, show = dict(r.split("=") for r in opt.rename), opt.show
     old, new = kernels(opt.old), kernels(opt.new)
@@ -67,6 +71,12 @@ def main(argv):
         bad += bool(nb or nd)
         print(f"{'DIFF' if nb or nd else 'same'}  {k1}  {len(b1)} instructions"
               + (f"  body lines differing: {nb}, descriptor lines: {nd}" if nb or nd else ""))
+        if opt.ops and (nb or nd):
+            c0, c1 = (collections.Counter(re.sub(r"_e(32|64)$", "", x.split()[0]) for x in b if x[0] != "." and x[-1] != ":") for b in (b0, b1))
+            ops = sorted(o for o in c0.keys() | c1.keys() if c0[o] != c1[o] and o not in ("s_nop", "s_waitcnt"))
+            fp = [o for o in ops if re.search(r"_f(16|32|64)", o)]
+            print("      opcode counts differing: " + (", ".join(f"{o} {c0[o]}->{c1[o]}" for o in ops) or "none"))
+            print("      floating-point opcodes among them: " + (", ".join(fp) or "none"))
         if show == k1:
             print("\n".join(x for x in difflib.unified_diff(b0 + d0, b1 + d1, lineterm="", n=0)))
     for k in new:
