@@ -19,6 +19,18 @@ int orbmi_debug_fast_candidates(orbmi_extractor* h, int item, int level, int* xy
  * xyr = {x, y, score} triples. */
 int orbmi_debug_octree_level(orbmi_extractor* h, int item, int level, int* xyr, int cap, int* n_out);
 
+/* Overwrites the device-resident keypoints, descriptors (n x 32 bytes) and count of batch item
+ * `item` of the handle's last extraction (its internal buffers after orbmi_extract, the caller's
+ * device buffers after orbmi_extract_batch_*) with n host keypoints, on the handle's stream, so a
+ * test can put chosen keypoints in front of orbmi_compute_stereo_matches*.  The pyramids the SAD
+ * stage reads stay those of the extracted images.  ORBMI_E_STATE before any extraction or for an
+ * item outside the last batch, ORBMI_E_CAP when n exceeds the last extraction's capacity,
+ * ORBMI_E_ARG for a keypoint whose octave lies outside the handle's levels or whose x, y lie
+ * outside the extracted image (the kernels index by them).  Beyond that the keypoints must be
+ * legal for the reference, which the caller sees to: y +- 2 * scale[octave] inside
+ * [0, rows - 1] (the reference indexes its row table unchecked; the kernels clamp the band). */
+int orbmi_debug_set_keypoints(orbmi_extractor* h, int item, const orbmi_keypoint* kps, const uint8_t* desc, int n);
+
 /* One PoseOptimization launch (orbmi_pose_optimization semantics, device arrays, one frame)
  * with an event trace in shader-clock cycles (s_memtime), trace = 16 + 64 * 8 * 8 words:
  * [0] total cycles, [1] total s_memrealtime ticks (100 MHz), [2] edge passes of wave 0; per

@@ -442,6 +442,32 @@ extern "C" int orbmi_debug_fast_candidates(orbmi_extractor* h, int item, int lev
     return n > cap ? ORBMI_E_CAP : ORBMI_OK;
 }
 
+extern "C" int orbmi_debug_set_keypoints(orbmi_extractor* h, int item, const orbmi_keypoint* kps,
+                                         const uint8_t* desc, int n) {
+    if (!h || n < 0 || (n > 0 && (!kps || !desc))) return ORBMI_E_ARG;
+    Extractor& e = h->ex;
+    if (e.levels.empty() || !e.last_kps || !e.last_desc || !e.last_counts || item < 0 || item >= e.last_batch)
+        return ORBMI_E_STATE;
+    if (n > e.last_capacity) return ORBMI_E_CAP;
+    // the stereo kernels index the scale table and the levels by octave and the row table by y
+    for (int i = 0; i < n; i++) {
+        const orbmi_keypoint& k = kps[i];
+        if (k.octave < 0 || k.octave >= e.nlevels || !(k.x >= 0.f && k.x <= (float)(e.cols - 1)) ||
+            !(k.y >= 0.f && k.y <= (float)(e.rows - 1)))
+            return ORBMI_E_ARG;
+    }
+    ORBMI_HIP(hipSetDevice(e.device));
+    const size_t at = (size_t)item * e.last_capacity;
+    if (n > 0) {
+        ORBMI_HIP(hipMemcpyAsync(e.last_kps + at, kps, (size_t)n * sizeof(orbmi_keypoint), hipMemcpyHostToDevice,
+                                 e.stream));
+        ORBMI_HIP(hipMemcpyAsync(e.last_desc + at * 32, desc, (size_t)n * 32, hipMemcpyHostToDevice, e.stream));
+    }
+    ORBMI_HIP(hipMemcpyAsync(e.last_counts + item, &n, sizeof(int), hipMemcpyHostToDevice, e.stream));
+    ORBMI_HIP(hipStreamSynchronize(e.stream));  // the host arrays and n are the caller's again on return
+    return ORBMI_OK;
+}
+
 extern "C" int orbmi_debug_octree_level(orbmi_extractor* h, int item, int level, int* xyr, int cap, int* n_out) {
     if (!h || !n_out || (cap > 0 && !xyr)) return ORBMI_E_ARG;
     Extractor& e = h->ex;

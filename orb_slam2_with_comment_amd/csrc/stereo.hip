@@ -4,6 +4,7 @@
 //                    one wave per left keypoint
 //   k_stereo_filter  median(SAD) * 2.1 outlier cull (:661-674)          one workgroup
 #include <algorithm>
+#include <cmath>
 
 #include "extractor.h"
 
@@ -197,14 +198,16 @@ __global__ __launch_bounds__(256) void k_stereo_match(StereoArgs a) {
 }
 
 // sort(vDistIdx); median = vDistIdx[size/2].first; drop dist >= 1.5f*1.4f*median
-// The median is a two-pass radix select over the SAD values (0 <= SAD <= 121 * 255 < 2^15):
-// a 256-bin histogram of v >> 7 finds the bin holding rank size/2, a 128-bin histogram of the
-// low bits inside it finds the value.  The values stay in registers between the passes.
+// The median is a two-pass radix select over the SAD values.  Both patches have their centre
+// pixel subtracted before the L1 norm, so a term reaches 2 * 255 and 0 <= SAD <= 121 * 510 =
+// 61,710 < 2^16: a 256-bin histogram of v >> 8 finds the bin holding rank size/2, a 256-bin
+// histogram of the low byte inside it finds the value.  The values stay in registers between
+// the passes.
 constexpr int kFilterRegs = 8;  // values per thread held in registers (8192 keypoints)
 __global__ __launch_bounds__(1024) void k_stereo_filter(const int* __restrict__ countL, int capL,
                                                         const int* __restrict__ sad, float* __restrict__ u_right,
                                                         float* __restrict__ depth) {
-    __shared__ int h1[256], h2[128], sel[2];
+    __shared__ int h1[256], h2[256], sel[2];
     const int tid = threadIdx.x;
     const int n = min(*countL, capL);
     int v[kFilterRegs];
@@ -218,10 +221,9 @@ __global__ __launch_bounds__(1024) void k_stereo_filter(const int* __restrict__ 
         for (int k = 0; k < kFilterRegs; k++) f(tid + k * 1024, v[k]);
         for (int i = tid + kFilterRegs * 1024; i < n; i += 1024) f(i, sad[i]);
     };
-    if (tid < 256) h1[tid] = 0;
-    if (tid < 128) h2[tid] = 0;
+    if (tid < 256) { h1[tid] = 0; h2[tid] = 0; }
     __syncthreads();
-    for_values([&](int, int x) { if (x >= 0) atomicAdd(&h1[min(x >> 7, 255)], 1); });
+    for_values([&](int, int x) { if (x >= 0) atomicAdd(&h1[min(x >> 8, 255)], 1); });
     __syncthreads();
     auto select = [&](const int* h, int nb, int rank_in, int* bin, int* rest, int* total) {
         // wave 0: bins in lane order (nb / 64 per lane), prefix, the bin holding rank_in
@@ -246,12 +248,12 @@ __global__ __launch_bounds__(1024) void k_stereo_filter(const int* __restrict__ 
     __syncthreads();
     const int b1 = sel[0], r1 = sel[1];
     if (b1 < 0) return;
-    for_values([&](int, int x) { if (x >= 0 && (x >> 7) == b1) atomicAdd(&h2[x & 127], 1); });
+    for_values([&](int, int x) { if (x >= 0 && (x >> 8) == b1) atomicAdd(&h2[x & 255], 1); });
     __syncthreads();
     if (tid < 64) {
         int bin = -1, rest = 0, M = 0;
-        select(h2, 128, r1, &bin, &rest, &M);
-        if (bin >= 0) sel[0] = (b1 << 7) | bin;
+        select(h2, 256, r1, &bin, &rest, &M);
+        if (bin >= 0) sel[0] = (b1 << 8) | bin;
     }
     __syncthreads();
     const float median = (float)sel[0];
@@ -267,7 +269,10 @@ int stereo_run(Extractor& Lx, int itemL, Extractor& Rx, int itemR, float bf, flo
     const int nrows = Lx.levels[0].H;
     if (nrows + 1 > kStereoRowsMax) return ORBMI_E_UNSUPPORTED;
     const int capR = Rx.last_capacity, capL = Lx.last_capacity;
-    const int list_cap = capR * 24;  // rows per right keypoint <= 2*ceil(2*scale)+2
+    // a right keypoint enters rows floor(y - r) .. ceil(y + r), r = 2 * scale[octave]: at most
+    // ceil(4 * scale) + 2 of them (and never more than the image has), so the list cannot overfill
+    const float smax = *std::max_element(Lx.scale.begin(), Lx.scale.end());
+    const int list_cap = capR * std::min((int)std::ceil(4.0f * smax) + 2, nrows);
     int rc;
     if ((rc = ensure_buf(&Lx.d_row_start, &Lx.row_cap, (size_t)nrows + 1))) return rc;
     if ((rc = ensure_buf(&Lx.d_row_list, &Lx.row_list_cap, (size_t)list_cap))) return rc;
