@@ -43,7 +43,8 @@ int orbmi_debug_pose_trace(orbmi_pose* h, orbmi_pose_frame* frames, const orbmi_
 /* k_greedy (the order-dependent exclusion of SearchByProjection) since the last reset, summed
  * over every matcher of the process: out = {calls, rounds, largest round count, slow-path query
  * evaluations, calls that fell back to the sequential replay}; synchronises the device.  The
- * kernels collect these (and orbmi_debug_greedy_cycles) only after the first call of either. */
+ * kernels collect these (and orbmi_debug_greedy_cycles) only after the first call of either;
+ * reset < 0 reads, clears and switches the collection off again. */
 int orbmi_debug_greedy_stats(unsigned long long* out, int reset);
 
 /* k_greedy's s_memtime cycles summed over calls since the last reset: out[0] prologue (queries'

@@ -577,7 +577,7 @@ __device__ inline int greedy_decide_pe(const GreedyArgs& a, unsigned e1, unsigne
 // k_greedy statistics (orbmi_debug_greedy_stats): calls, rounds summed, largest round count,
 // slow-path query evaluations summed, calls that fell back to the sequential replay
 __device__ unsigned long long g_greedy_stats[5];
-__device__ int g_greedy_on;  // set by the first orbmi_debug_greedy_* call: statistics collected from then on
+__device__ int g_greedy_on;  // set by an orbmi_debug_greedy_* call: statistics collected until greedy_stats(., < 0)
 // development aid: s_memtime cycles of k_greedy's phases summed over calls (prologue, rounds,
 // epilogue; thread 0's split of the rounds: claims + barrier, evaluation, flag + barrier), read by
 // orbmi_debug_greedy_cycles
@@ -983,7 +983,7 @@ int greedy_cycles(unsigned long long out[7], int reset) {
 
 int greedy_stats(unsigned long long out[5], int reset) {
     ORBMI_HIP(hipDeviceSynchronize());
-    const int on = 1;
+    const int on = reset >= 0;  // reset < 0: read, clear and stop collecting (the state before the first call)
     ORBMI_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_greedy_on), &on, sizeof(on)));
     ORBMI_HIP(hipMemcpyFromSymbol(out, HIP_SYMBOL(g_greedy_stats), sizeof(unsigned long long) * 5));
     if (reset) {
