@@ -971,6 +971,29 @@ int orbmi_search_by_sim3(orbmi_matcher* m, const orbmi_frame_view* KF1, const or
 int orbmi_search_by_projection_sim3(orbmi_matcher* m, const orbmi_frame_view* KF, const float* Scw,
                                     const orbmi_mappoint* mps, int n, int32_t* matched, float th, int* nmatches);
 
+/* ---- LoopClosing::SearchAndFuse: ORBmatcher::Fuse(KF, Scw) --------------------------- */
+
+/* ORBmatcher::Fuse(pKF, Scw, vpPoints, th, vpReplacePoint) (src/ORBmatcher.cc:1139-1269), its
+ * search, for the nkf keyframes of LoopClosing::SearchAndFuse in one launch: the same n_mp points
+ * (vpPoints, the loop map points) projected into keyframe kfs[k] under its own Sim3
+ * Scw[12 k .. 12 k + 11] (rows 0-2 of [sRcw | t], row-major, host memory) and compared with its
+ * keypoints.  in_kf (nkf x n_mp, may be NULL): in_kf[k * n_mp + i] = vpPoints[i]->IsInKeyFrame(
+ * kfs[k]) (spAlreadyFound); isBad() as ORBMI_MP_BAD.  best_idx[k * n_mp + i] = the keypoint of
+ * least descriptor distance in the window (the first in the reference's visit order on ties) when
+ * that distance is <= TH_LOW = 50, else -1; best_dist[k * n_mp + i] = that distance, 256 without
+ * a candidate (orbmi_fuse_search's convention).  Unlike orbmi_fuse_search there is no chi2 gate
+ * on the reprojection error; unlike orbmi_search_by_projection_sim3 a keypoint that already holds
+ * a map point is a candidate and two points may choose one keypoint.  nfused[k] (host, may be
+ * NULL) = the points of keyframe k with best_idx >= 0.  The keyframes' poses are not read.  The
+ * map updates (:1247-1266) are the caller's replay of best_idx in list order.
+ * ORBMI_E_ARG: a NULL array that is needed, a negative count, Scw in device memory, or an Scw
+ * whose first row has norm 0 or is not finite -- checked before anything is launched or written.
+ * nkf == 0 or n_mp == 0: ORBMI_OK, nothing launched or written.  ORBMI_E_UNSUPPORTED above 16384
+ * keypoints, as orbmi_fuse_search. */
+int orbmi_fuse_sim3_search_batch(orbmi_matcher* m, int nkf, const orbmi_frame_view* kfs, const float* Scw,
+                                 const orbmi_mappoint* mps, const uint8_t* in_kf, int n_mp, float th,
+                                 int32_t* best_idx, int32_t* best_dist, int* nfused);
+
 /* ---- LoopClosing::ComputeSim3: Optimizer::OptimizeSim3 ------------------------------- */
 
 /* One OptimizeSim3 problem after the reference's assembly loop (src/Optimizer.cc:1198-1281): the n

@@ -247,6 +247,26 @@ public:
         return n;
     }
 
+    // The search of Fuse(KeyFrame*, cv::Mat Scw, const vector<MapPoint*>& vpPoints, float th,
+    // vector<MapPoint*>& vpReplacePoint) (src/ORBmatcher.cc:1139-1269) for the keyframes of
+    // LoopClosing::SearchAndFuse in one call: Scw = KFs.size() x 12 floats (rows 0-2 of each
+    // keyframe's [sRcw | t]), inKeyFrame KFs.size() x mps.size() flags or empty; keyframe k's
+    // results at bestIdx / bestDist[k * mps.size() ..), its count of bestIdx >= 0 at nFused[k].
+    // The caller replays the map updates in list order, keyframe by keyframe
+    void FuseSearch(const std::vector<orbmi_frame_view>& KFs, const float* Scw, const std::vector<orbmi_mappoint>& mps,
+                    const std::vector<uint8_t>& inKeyFrame, float th, std::vector<int32_t>& bestIdx,
+                    std::vector<int32_t>& bestDist, std::vector<int>& nFused) {
+        const size_t total = KFs.size() * mps.size();
+        if (!inKeyFrame.empty() && inKeyFrame.size() != total) throw Error(ORBMI_E_ARG, "ORBmatcher::FuseSearch(KFs, Scw)");
+        bestIdx.assign(total, -1);
+        bestDist.assign(total, 256);
+        nFused.assign(KFs.size(), 0);
+        check(orbmi_fuse_sim3_search_batch(h_, (int)KFs.size(), KFs.data(), Scw, mps.data(),
+                                           inKeyFrame.empty() ? nullptr : inKeyFrame.data(), (int)mps.size(), th,
+                                           bestIdx.data(), bestDist.data(), nFused.data()),
+              "orbmi_fuse_sim3_search_batch");
+    }
+
     // SearchBySim3(KeyFrame*, KeyFrame*, vector<MapPoint*>& vpMatches12, s12, R12, t12, th)
     // (src/ORBmatcher.cc:1285-1525): mps / hasMapPoint one record and flag per keypoint slot,
     // match12 as orbmi.h codes vpMatches12 (-1 none, >= 0 the KF2 slot, -2 a point without an index

@@ -133,6 +133,7 @@ _PROTOS = {
     "orbmi_sim3_sample_triples": (_i, [C.c_uint64, _i, _i, _i, _vp]),
     "orbmi_sim3_max_error": (_i, [_f, C.POINTER(C.c_int32)]),
     "orbmi_optimize_sim3_batch": (_i, [_vp, _i, _vp, _vp]),
+    "orbmi_fuse_sim3_search_batch": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _i, _f, _vp, _vp, _vp]),
     "orbmi_search_by_projection_sim3": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _f, C.POINTER(_i)]),
     "orbmi_debug_sim3_opt_linearize": (_i, [_vp, _vp, _vp, _vp, _vp]),
     "orbmi_search_by_bow_kf": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _i, _vp, C.POINTER(_i)]),

@@ -1304,6 +1304,64 @@ int orbmi_search_by_projection_sim3(orbmi_matcher* h, const orbmi_frame_view* kf
     return ORBMI_OK;
 }
 
+int orbmi_fuse_sim3_search_batch(orbmi_matcher* h, int nkf, const orbmi_frame_view* kfs, const float* Scw,
+                                 const orbmi_mappoint* mps, const uint8_t* in_kf, int n_mp, float th, int32_t* best_idx,
+                                 int32_t* best_dist, int* nfused) {
+    if (!h || nkf < 0 || n_mp < 0 || (nkf > 0 && (!kfs || !Scw || on_device(Scw))) ||
+        (nkf > 0 && n_mp > 0 && (!mps || !best_idx || !best_dist)))
+        return ORBMI_E_ARG;
+    // Scw = [sRcw | t] per keyframe: scw = sqrt(row 0 . row 0) (the dot product in double, rounded
+    // to float), Rcw = sRcw / scw, tcw = t / scw, Ow = -Rcw^T tcw (:1148-1153), float; once per
+    // keyframe, as orbmi_search_by_projection_sim3 does it
+    std::vector<orbmi::FuseSim3Pose> poses((size_t)nkf);
+    for (int k = 0; k < nkf; k++) {
+        const float* S = Scw + 12 * (size_t)k;
+        orbmi::FuseSim3Pose& P = poses[k];
+        const float scw = (float)sqrt(((double)S[0] * S[0] + (double)S[1] * S[1]) + (double)S[2] * S[2]);
+        if (!(scw > 0.0f) || !std::isfinite(scw)) return ORBMI_E_ARG;
+        for (int q = 0; q < 12; q++) P.T[q] = S[q] / scw;
+        for (int c = 0; c < 3; c++) P.Ow[c] = -((P.T[c] * P.T[3] + P.T[4 + c] * P.T[7]) + P.T[8 + c] * P.T[11]);
+    }
+    if (nkf == 0 || n_mp == 0) return ORBMI_OK;
+    Matcher& m = h->m;
+    ORBMI_HIP(hipSetDevice(m.device));
+    m.arena_reset();
+    int rc = 0;
+    const orbmi_mappoint* d_mps = dev_in(m, mps, (size_t)n_mp, &rc);
+    const uint8_t* d_in = dev_in(m, in_kf, in_kf ? (size_t)n_mp * nkf : 0, &rc);
+    if (rc) return rc;
+    std::vector<FuseKF> K(nkf);
+    for (int k = 0; k < nkf; k++) {
+        memset(&K[k], 0, sizeof(FuseKF));
+        if ((rc = make_frame(m, &kfs[k], &K[k].F, false))) return rc;  // the pose is Scw's
+        K[k].in_kf = d_in ? d_in + (size_t)k * n_mp : nullptr;
+    }
+    FuseKF* d_k = (FuseKF*)m.stage(sizeof(FuseKF) * nkf);
+    orbmi::FuseSim3Pose* d_p = (orbmi::FuseSim3Pose*)m.stage(sizeof(orbmi::FuseSim3Pose) * nkf);
+    int* d_cnt = (int*)m.stage(sizeof(int) * nkf);
+    std::vector<OutBuf> outs;
+    int* d_bi = dev_out(m, best_idx, (size_t)n_mp * nkf, outs);
+    int* d_bd = dev_out(m, best_dist, (size_t)n_mp * nkf, outs);
+    if (!d_k || !d_p || !d_cnt || !d_bi || !d_bd) return ORBMI_E_HIP;
+    int ncap = 0;
+    if ((rc = orbmi::fuse_multi_prepare(m, nkf, K.data(), n_mp, d_bi, d_bd, d_cnt, &ncap))) return rc;
+    ORBMI_HIP(m.h2d(d_k, K.data(), sizeof(FuseKF) * nkf));
+    ORBMI_HIP(m.h2d(d_p, poses.data(), sizeof(orbmi::FuseSim3Pose) * nkf));
+    if ((rc = orbmi::launch_fuse_sim3(m, nkf, d_k, d_p, d_mps, n_mp, th, ncap))) return rc;
+    bool wait = false;
+    ORBMI_HIP(m.flush_up());
+    if (m.up_err != hipSuccess) return ORBMI_E_HIP;
+    for (OutBuf& o : outs)
+        if (o.bytes) { ORBMI_HIP(m.d2h(o.user, o.dev, o.bytes)); wait = true; }
+    if (nfused) {
+        ORBMI_HIP(m.d2h(nfused, d_cnt, sizeof(int) * nkf));
+        wait = true;
+    }
+    if (wait) ORBMI_HIP(hipStreamSynchronize(m.ls()));
+    m.d2h_flush();
+    return ORBMI_OK;
+}
+
 namespace {
 
 bool sim3_opt_args_ok(const orbmi_sim3_opt_problem& P) {

@@ -73,6 +73,12 @@ struct FuseKF {
     int* ncand;             // one int
 };
 
+// Keyframe k's decomposed Scw of a batched Fuse(KF, Scw) search, beside its FuseKF
+struct FuseSim3Pose {
+    float T[12];   // [Rcw | tcw] = [sRcw | t] / scw
+    float Ow[3];   // -Rcw^T tcw
+};
+
 // One direction of SearchBySim3 (grid row): the source keyframe's points searched in the target
 // keyframe F
 struct Sim3Side {
@@ -220,6 +226,8 @@ int fuse_multi_prepare(Matcher& m, int nkf, FuseKF* kfs_host, int n, int* best_i
 // kfs_host == nullptr: the table is already prepared (fuse_multi_prepare -> ncap) and uploaded
 int launch_fuse_multi(Matcher& m, int nkf, FuseKF* kfs_host, FuseKF* kfs_dev, const orbmi_mappoint* mps, int n,
                       float th, int* best_idx, int* best_dist, int* ncand, int ncap = 0);
+int launch_fuse_sim3(Matcher& m, int nkf, const FuseKF* kfs_dev, const FuseSim3Pose* poses_dev, const orbmi_mappoint* mps,
+                     int n, float th, int ncap);
 int launch_search_by_sim3(Matcher& m, Sim3Side* sides_host, Sim3Side* sides_dev, int* match12, uint8_t* already2, float th,
                           int* nfound);
 int launch_proj_sim3(Matcher& m, const DevFrame& F, const ProjSim3Args& a);

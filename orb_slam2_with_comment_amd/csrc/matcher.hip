@@ -11,6 +11,7 @@
 //   k_triangulate[_par] CreateNewMapPoints' triangulation of the matches       thread / (keypoint, pair)
 //   k_fuse[_multi]      Fuse(KF, MPs): the search, 8 lanes per point, one or several keyframes
 //   k_grid_build_multi  the grids of a batched Fuse's keyframes                  workgroup / keyframe
+//   k_fuse_sim3         Fuse(KF, Scw): the search under each keyframe's own Sim3, several keyframes
 //   k_sim3_grids / _search / _agree   SearchBySim3: both grids, both directions, the agreement
 //   k_proj_sim3         SearchByProjection(KF, Scw): candidate lists for the host's replay
 //   k_patch_desc        recomputed descriptors into map-point records
@@ -1986,6 +1987,58 @@ int launch_fuse_multi(Matcher& m, int nkf, FuseKF* kfs_host, FuseKF* kfs_dev, co
     if (n > 0)
         hipLaunchKernelGGL(k_fuse_multi, dim3((n * kFuseLanes + 255) / 256, nkf), dim3(256), 0, m.ls(), kfs_dev, mps, n,
                            th);
+    return hipGetLastError() == hipSuccess ? ORBMI_OK : ORBMI_E_HIP;
+}
+
+// ------------------------------------------------------------------------ Fuse(KF, Scw)
+// ORBmatcher::Fuse(KeyFrame*, cv::Mat Scw, vpPoints, th, vpReplacePoint), the search
+// (src/ORBmatcher.cc:1139-1246), one list of points against several keyframes (grid row =
+// keyframe, eight lanes per point).  The keyframe query of SearchByProjection(KF, Scw) under
+// keyframe k's own decomposed Scw (poses[k]); against k_fuse no chi2 gate on the reprojection
+// error, against k_proj_sim3 no occupancy: a keypoint that holds a map point is a candidate and
+// two points may pick one keypoint, so the kernel decides.  Outputs as k_fuse's; the map updates
+// (:1247-1266) are the caller's replay in list order.
+__global__ __launch_bounds__(256) void k_fuse_sim3(const FuseKF* __restrict__ kfs, const FuseSim3Pose* __restrict__ poses,
+                                                   const orbmi_mappoint* __restrict__ mps, int n, float th) {
+    const int t = blockIdx.x * blockDim.x + threadIdx.x, i = t / kFuseLanes, glane = t % kFuseLanes;
+    const FuseKF& K = kfs[blockIdx.y];
+    const FuseSim3Pose& P = poses[blockIdx.y];
+    const DevFrame& F = K.F;
+    const bool valid = i < n;  // the other lanes only take part in the group minimum
+    const orbmi_mappoint mp = mps[valid ? i : 0];
+    bool ok = valid && !(mp.flags & ORBMI_MP_BAD) && !(K.in_kf && K.in_kf[i]);
+    float Pc[3] = {0, 0, 0};
+    if (ok) {
+        transform(P.T, mp.pos, Pc);
+        ok = !(Pc[2] < 0.0f);
+    }
+    float u = 0, v = 0, invz = 0, dist3D = 0;
+    if (ok) ok = kf_project(F, F.fx, F.fy, F.cx, F.cy, Pc, &u, &v, &invz);
+    if (ok) {
+        const float PO[3] = {mp.pos[0] - P.Ow[0], mp.pos[1] - P.Ow[1], mp.pos[2] - P.Ow[2]};
+        dist3D = (float)sqrt((double)PO[0] * PO[0] + (double)PO[1] * PO[1] + (double)PO[2] * PO[2]);
+        ok = in_distance_range(mp, dist3D) && in_viewing_cone(mp, PO, dist3D);
+    }
+    const unsigned long long best =
+        windowed_best<kFuseLanes>(F, K.cs, K.cl, mp, ok, u, v, dist3D, th, glane,
+                                  [](int, const orbmi_keypoint&) { return true; }, [](int, unsigned long long) {});
+    if (!valid || glane != 0) return;
+    const int bd = best != ~0ull ? (int)(best >> 40) : 256, bi = best != ~0ull ? (int)(best & 0xFFFFF) : -1;
+    const bool fused = bi >= 0 && bd <= TH_LOW;
+    K.best_idx[i] = fused ? bi : -1;
+    K.best_dist[i] = bd;
+    wave_count_add(K.ncand, fused);
+}
+
+// kfs_dev: the table of fuse_multi_prepare, uploaded (the grids are built here, which also zeroes
+// the counts); poses_dev: one decomposed Scw per keyframe
+int launch_fuse_sim3(Matcher& m, int nkf, const FuseKF* kfs_dev, const FuseSim3Pose* poses_dev, const orbmi_mappoint* mps,
+                     int n, float th, int ncap) {
+    if (nkf <= 0) return ORBMI_OK;
+    hipLaunchKernelGGL(k_grid_build_multi, dim3(nkf), dim3(1024), 0, m.ls(), kfs_dev, m.d_mkp_cell, ncap);
+    if (n > 0)
+        hipLaunchKernelGGL(k_fuse_sim3, dim3((n * kFuseLanes + 255) / 256, nkf), dim3(256), 0, m.ls(), kfs_dev, poses_dev,
+                           mps, n, th);
     return hipGetLastError() == hipSuccess ? ORBMI_OK : ORBMI_E_HIP;
 }
 

@@ -13,9 +13,17 @@ propagate_corrected_sim3  CorrectLoop's pose propagation: CorrectedSim3 and NonC
 optimize_essential_graph  the edge list, the device pose-graph Levenberg and the correction of
                           poses and map points: the arithmetic of LoopClosing::CorrectLoop.
 
-The covisibility graph stays the caller's: it comes in as callables (or mappings) from a keyframe
-id to ids.  CorrectLoop's map surgery (Fuse(KF, Scw), MapPoint::Replace, UpdateConnections), global
-BA and DetectRelocalizationCandidates are not here.
+
+fuse_sim3_replay          the map updates of ORBmatcher::Fuse(KF, Scw) in list order.
+search_and_fuse           LoopClosing::SearchAndFuse: one batched search, the replay per keyframe.
+loop_connections          the new covisibility links of CorrectLoop (LoopConnections).
+current_matched_points    mvpCurrentMatchedPoints as objects, from compute_sim3's result.
+correct_loop              LoopClosing::CorrectLoop on system.KeyFrame / system.MapPoint, from the
+                          accepted Scw to the corrected poses and points.
+
+For detection the covisibility graph stays the caller's: it comes in as callables (or mappings)
+from a keyframe id to ids.  Global BA, monocular mode, DetectRelocalizationCandidates and the
+call from the SLAM loops are not here.
 """
 from __future__ import annotations
 
@@ -24,7 +32,8 @@ import ctypes as C
 import numpy as np
 
 from ._capi import check, lib
-from .sim3 import DeviceBackend, compute_sim3
+from .sim3 import DeviceBackend, _quat_to_R, compute_sim3
+from .types import MAPPOINT_DTYPE, MP_BAD, MP_HAS_OBS, Frame
 from .vocabulary import L1_NORM
 
 
@@ -176,6 +185,28 @@ class LoopBackend(DeviceBackend):
         """ORBmatcher matcher(0.75, true); matcher.SearchByBoW(mpCurrentKF, pKF, ...) (:299, :330)."""
         return self.matcher.SearchByBoWKF(cur["kf"], cur["ok"], cur["fv"], cand["kf"], cand["ok"], cand["fv"],
                                           nnratio=0.75, checkOri=True)
+
+    # CorrectLoop's operators: the batched Fuse(KF, Scw) search, ComputeDistinctiveDescriptors and
+    # the essential graph's three, all on this backend's matcher handle
+    def fuse_sim3_search(self, kfs, Scws, mps, in_kf, th):
+        return self.matcher.FuseSim3Search(kfs, Scws, mps, in_kf, th)
+
+    def distinctive(self, obs_desc, obs_off):
+        return self.matcher.ComputeDistinctiveDescriptors(obs_desc, obs_off)[1]
+
+    def _essgraph(self):
+        if getattr(self, "_eg", None) is None:
+            self._eg = EssGraphBackend(matcher=self.matcher)
+        return self._eg
+
+    def essential_graph_edges(self, G):
+        return self._essgraph().essential_graph_edges(G)
+
+    def optimize_essential_graph(self, vertices, fixed, v0, v1, meas, fix_scale, iterations=20):
+        return self._essgraph().optimize_essential_graph(vertices, fixed, v0, v1, meas, fix_scale, iterations)
+
+    def correct_points_sim3(self, points, ref_index, Srw, Swr_corrected, poses):
+        return self._essgraph().correct_points_sim3(points, ref_index, Srw, Swr_corrected, poses)
 
 
 class LoopDetector:
@@ -488,3 +519,245 @@ def optimize_essential_graph(graph, fix_scale, points=None, point_ref=None, back
     finally:
         if own:
             be.close()
+
+
+# ---- LoopClosing::CorrectLoop: the map surgery --------------------------------------
+# On system.KeyFrame / system.MapPoint.  `backend`: LoopBackend, or an object of the same methods
+# over a restatement (fuse_sim3_search, distinctive and the essential graph's three).
+
+def _kf_frame(kf) -> Frame:
+    return Frame(kf.keys_un, kf.desc, kf.u_right, kf.tcw, kf.cam, kf.scale_factors, bounds=getattr(kf, "bounds", None))
+
+
+def _fuse_records(mps) -> np.ndarray:
+    rec = np.zeros(len(mps), MAPPOINT_DTYPE)
+    for j, mp in enumerate(mps):
+        rec["pos"][j], rec["normal"][j], rec["desc"][j] = mp.pos, mp.normal, mp.desc
+        rec["max_distance"][j], rec["min_distance"][j] = mp.max_distance, mp.min_distance
+        rec["flags"][j] = (MP_BAD if mp.bad else 0) | (MP_HAS_OBS if mp.nobs > 0 else 0)
+    return rec
+
+
+def sim3_to_cv_scw(S) -> np.ndarray:
+    """Converter::toCvMat(g2o::Sim3): rows 0-2 of [s R | t], computed in double and rounded to
+    float once."""
+    S = np.asarray(S, np.float64).reshape(8)
+    out = np.zeros((3, 4), np.float32)
+    out[:, :3] = (S[7] * _quat_to_R(S[:4])).astype(np.float32)
+    out[:, 3] = S[4:7].astype(np.float32)
+    return out
+
+
+def _distinctive(mps, backend):
+    """MapPoint::ComputeDistinctiveDescriptors of the points that live, through the backend: the
+    descriptors of the observing keyframes that are not bad, in keyframe-id order."""
+    mps = [m for m in mps if not m.bad]
+    rows, off = [], [0]
+    for mp in mps:
+        for kf in sorted(mp.observations, key=lambda k: k.id):
+            if not kf.bad:
+                rows.append(kf.desc[mp.observations[kf]])
+        off.append(len(rows))
+    if not rows:
+        return
+    d = backend.distinctive(np.asarray(rows, np.uint8).reshape(-1, 32), np.asarray(off, np.int32))
+    for j, mp in enumerate(mps):
+        if off[j + 1] > off[j]:
+            mp.desc = np.asarray(d[j], np.uint8).copy()
+
+
+def fuse_sim3_replay(kf, pts, best_idx):
+    """The map updates of ORBmatcher::Fuse(pKF, Scw, vpPoints, th, vpReplacePoint)
+    (src/ORBmatcher.cc:1247-1266) from the search's best_idx, in list order: a point that is bad or
+    in kf by now is skipped; best_idx < 0 does nothing; else nFused counts, and the keypoint's
+    slot, read as it is at that moment, decides: a point that is not bad becomes replace[i], a bad
+    one changes nothing, an empty slot takes the point (AddObservation + AddMapPoint).
+    -> (replace: vpReplacePoint, nfused)."""
+    replace, nfused = [None] * len(pts), 0
+    for i, mp in enumerate(pts):
+        b = int(best_idx[i])
+        if mp.bad or kf in mp.observations or b < 0:
+            continue
+        nfused += 1
+        in_kf = kf.map_points[b]
+        if in_kf is not None:
+            if not in_kf.bad:
+                replace[i] = in_kf
+        else:
+            mp.add_observation(kf, b)
+            kf.map_points[b] = mp
+    return replace, nfused
+
+
+def search_and_fuse(corrected, loop_points, backend, th=4.0):
+    """LoopClosing::SearchAndFuse (src/LoopClosing.cc:725-754): corrected = CorrectedPosesMap as
+    {KeyFrame: Sim3}, taken in ascending keyframe id; loop_points = mvpLoopMapPoints.  Per keyframe:
+    Fuse(pKF, cvScw, loop points, 4, vpReplacePoints), then vpReplacePoints[i]->Replace(loop point
+    i) in index order, then the descriptors Replace owes its targets, once per keyframe.
+
+    The search of all keyframes runs in one launch up front on the records as they are.  Between
+    two keyframes a loop point's record changes only in its descriptor (a Replace onto it) and in
+    its bad flag; bad and in-keyframe are re-checked by the replay, and a live point whose record
+    differs from the one searched is searched again against the keyframes still to come, so the map
+    after the call is the one the keyframe-by-keyframe loop leaves.
+    -> one dict per keyframe: {"kf", "nfused", "added", "replaced", "researched"}."""
+    kfs = sorted(corrected, key=lambda k: k.id)
+    pts = list(loop_points)
+    nkf, n = len(kfs), len(pts)
+    if nkf == 0 or n == 0:
+        return [{"kf": k.id, "nfused": 0, "added": 0, "replaced": 0, "researched": 0} for k in kfs]
+    frames = [_kf_frame(k) for k in kfs]
+    Scws = [sim3_to_cv_scw(corrected[k]) for k in kfs]
+    rec0 = _fuse_records(pts)
+    in0 = np.array([[k in mp.observations for mp in pts] for k in kfs], np.uint8)
+    best = np.array(backend.fuse_sim3_search(frames, Scws, rec0, in0, th)[0], np.int32).reshape(nkf, n)
+    out = []
+    for t, kf in enumerate(kfs):
+        rec = _fuse_records(pts)
+        redo = [j for j, m in enumerate(pts) if not m.bad and rec[j].tobytes() != rec0[j].tobytes()]
+        if redo:
+            rin = np.array([[k in pts[j].observations for j in redo] for k in kfs[t:]], np.uint8)
+            bi = backend.fuse_sim3_search(frames[t:], Scws[t:], rec[redo], rin, th)[0]
+            best[t:, redo] = np.asarray(bi, np.int32).reshape(nkf - t, len(redo))
+            rec0[redo] = rec[redo]
+        had = [kf in m.observations for m in pts]
+        replace, nfused = fuse_sim3_replay(kf, pts, best[t])
+        added = sum(1 for j, m in enumerate(pts) if not had[j] and kf in m.observations)
+        owed, replaced = [], 0
+        for i, rep in enumerate(replace):
+            if rep is not None and rep.replace(pts[i]):
+                replaced += 1
+                if pts[i] not in owed:
+                    owed.append(pts[i])
+        _distinctive(owed, backend)
+        out.append({"kf": kf.id, "nfused": nfused, "added": added, "replaced": replaced, "researched": len(redo)})
+    return out
+
+
+def loop_connections(connected):
+    """LoopConnections of CorrectLoop (src/LoopClosing.cc:665-692): per keyframe of
+    mvpCurrentConnectedKFs (in the given order), UpdateConnections, then its connected keyframes
+    minus its covisibles of before minus mvpCurrentConnectedKFs.
+    -> {id: {id: weight}}, the weight GetWeight's after the update (essential_graph_edges' format)."""
+    connected = list(connected)
+    own = set(connected)
+    out = {}
+    for kf in connected:
+        previous = set(kf.covisible)
+        kf.update_connections()
+        out[kf.id] = {k.id: int(kf.get_weight(k)) for k in sorted(kf.conn, key=lambda k: k.id)
+                      if k not in previous and k not in own}
+    return out
+
+
+def current_matched_points(sim3_result, matched_kf, loop_points):
+    """mvpCurrentMatchedPoints (src/LoopClosing.cc:430-470) as objects, one per keypoint slot of the
+    current keyframe, from compute_sim3's result: loop_matched >= 0 is an index into loop_points
+    (the list compute_sim3 searched, in its order), -2 a point of the matched keyframe outside that
+    list (its slot in `matches`), -1 none."""
+    lm, m12 = np.asarray(sim3_result["loop_matched"]), np.asarray(sim3_result["matches"])
+    out = [None] * len(lm)
+    for j in range(len(lm)):
+        if lm[j] >= 0:
+            out[j] = loop_points[int(lm[j])]
+        elif lm[j] == -2 and m12[j] >= 0:
+            out[j] = matched_kf.map_points[int(m12[j])]
+    return out
+
+
+def correct_loop(cur, matched_kf, Scw, current_matched, loop_points, keyframes, map_points, fix_scale, backend,
+                 iterations=20):
+    """LoopClosing::CorrectLoop (src/LoopClosing.cc:509-719) without the thread handshakes and
+    without the global bundle adjustment.  cur / matched_kf: mpCurrentKF / mpMatchedKF; Scw: mg2oScw
+    (8 doubles: q, t, s); current_matched: mvpCurrentMatchedPoints (current_matched_points);
+    loop_points: mvpLoopMapPoints; keyframes / map_points: the map's.  Keyframe-keyed maps are
+    walked in ascending id.
+    -> {"corrected_points" {kf id: count}, "loop_fusion" {"replaced", "added"}, "search_and_fuse",
+    "loop_connections", "graph", "essential_graph" (optimize_essential_graph's result)}."""
+    from .system import update_normals_and_depths
+    cur.update_connections()  # :540
+    connected = list(cur.covisible) + [cur]  # mvpCurrentConnectedKFs
+    n_ids = max(k.id for k in keyframes) + 1
+    Tcw = np.zeros((n_ids, 4, 4), np.float32)
+    Tcw[:] = np.eye(4, dtype=np.float32)
+    for k in keyframes:
+        Tcw[k.id] = np.asarray(k.tcw, np.float32).reshape(4, 4)
+    Scw = np.asarray(Scw, np.float64).reshape(8)
+    corrected, nonc = propagate_corrected_sim3(Tcw, cur.id, [k.id for k in cur.covisible], Scw, backend)  # :546-582
+    by_id = {k.id: k for k in connected}
+    order = sorted(corrected)
+    # :586-633.  A point is corrected through the first keyframe (ascending id) that holds it; the
+    # positions and the poses [R | t / s] of all of them come from one correct_points_sim3 call
+    todo, ref = [], []
+    seen = set()
+    per_kf = {}
+    for q, i in enumerate(order):
+        mine = []
+        for mp in by_id[i].map_points:
+            if mp is None or mp.bad or mp.corrected_by_kf == cur.id or mp in seen:
+                continue
+            seen.add(mp)
+            mine.append(mp)
+        per_kf[i] = mine
+        todo += mine
+        ref += [q] * len(mine)
+    Srw = np.array([nonc[i] for i in order], np.float64).reshape(-1, 8)
+    Sc = np.array([corrected[i] for i in order], np.float64).reshape(-1, 8)
+    Swr = np.array([_sim3_inverse(S) for S in Sc], np.float64).reshape(-1, 8)
+    P = np.array([mp.pos for mp in todo], np.float32).reshape(-1, 3)
+    newP, newT = backend.correct_points_sim3(P, np.asarray(ref, np.int32), Srw, Swr, Sc)
+    at = 0
+    for q, i in enumerate(order):
+        kf = by_id[i]
+        for mp in per_kf[i]:
+            mp.pos = np.asarray(newP[at], np.float32).copy()
+            mp.corrected_by_kf, mp.corrected_reference = cur.id, i
+            at += 1
+        # UpdateNormalAndDepth reads the centres of all observing keyframes as they are now: the
+        # earlier ones corrected, this one and the later ones not yet
+        update_normals_and_depths(per_kf[i])
+        kf.tcw = np.asarray(newT[q], np.float32).reshape(4, 4).copy()
+        kf.update_connections()
+    # :638-653, the loop fusion
+    fusion = {"replaced": 0, "added": 0}
+    for i, lp in enumerate(current_matched):
+        if lp is None:
+            continue
+        cm = cur.map_points[i]
+        if cm is not None:
+            if cm.replace(lp):
+                fusion["replaced"] += 1
+                _distinctive([lp], backend)
+        else:
+            cur.map_points[i] = lp
+            lp.add_observation(cur, i)
+            _distinctive([lp], backend)
+            fusion["added"] += 1
+    saf = search_and_fuse({by_id[i]: corrected[i] for i in order}, loop_points, backend)  # :661
+    lc = loop_connections(connected)  # :665-692
+    # Optimizer::OptimizeEssentialGraph over the map as it is now
+    live = np.zeros(n_ids, bool)
+    parent = np.full(n_ids, -1, np.int32)
+    for k in keyframes:
+        live[k.id] = not k.bad
+        Tcw[k.id] = np.asarray(k.tcw, np.float32).reshape(4, 4)
+        if k.parent is not None:
+            parent[k.id] = k.parent.id
+    G = {"live": live, "Tcw": Tcw, "parent": parent,
+         "loop_edges": {k.id: [e.id for e in k.loop_edges] for k in keyframes if k.loop_edges},
+         "covisibles": {k.id: [c.id for c in k.covisible if k.get_weight(c) >= 100] for k in keyframes if not k.bad},
+         "corrected": corrected, "noncorrected": nonc, "loop_connections": lc, "loop_id": matched_kf.id, "cur_id": cur.id}
+    pts = [mp for mp in map_points if not mp.bad]
+    refs = [mp.corrected_reference if mp.corrected_by_kf == cur.id else mp.ref_kf.id for mp in pts]
+    r = optimize_essential_graph(G, fix_scale, np.array([mp.pos for mp in pts], np.float32).reshape(-1, 3), refs,
+                                 backend=backend, iterations=iterations)
+    for k in keyframes:
+        if not k.bad:
+            k.tcw = np.asarray(r["Tcw"][k.id], np.float32).reshape(4, 4).copy()
+    for j, mp in enumerate(pts):
+        mp.pos = np.asarray(r["points"][j], np.float32).copy()
+    update_normals_and_depths(pts)
+    matched_kf.loop_edges.append(cur)  # :702-703
+    cur.loop_edges.append(matched_kf)
+    return {"corrected_points": {i: len(per_kf[i]) for i in order}, "loop_fusion": fusion, "search_and_fuse": saf,
+            "loop_connections": lc, "graph": G, "essential_graph": r}

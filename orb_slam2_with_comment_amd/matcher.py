@@ -10,7 +10,7 @@ import ctypes as C
 import numpy as np
 
 from ._capi import check, lib
-from .types import TRACK_DTYPE
+from .types import TRACK_DTYPE, FrameView
 
 
 class ORBmatcher:
@@ -113,6 +113,37 @@ class ORBmatcher:
             self._h, C.addressof(v), mps.ctypes.data if n else None, None if ink is None else ink.ctypes.data, n,
             th, bi.ctypes.data, bd.ctypes.data, C.byref(c)))
         return bi[:n], bd[:n], c.value
+
+    def FuseSim3Search(self, kfs, Scws, mps, in_kf=None, th=4.0):
+        """The search of Fuse(KeyFrame*, cv::Mat Scw, vpPoints, th, vpReplacePoint)
+        (src/ORBmatcher.cc:1139-1269) for several keyframes in one launch: kfs are types.Frame,
+        Scws one 3x4 or 4x4 float matrix [sRcw | t] per keyframe, mps the loop map points
+        (orbmi_mappoint records), in_kf (nkf, n) IsInKeyFrame flags or None.
+        -> (best_idx, best_dist) of shape (nkf, n) and nfused (nkf); the Replace / AddObservation
+        replay in list order is the caller's (loop.fuse_sim3_replay)."""
+        mps = np.ascontiguousarray(mps)
+        nkf, n = len(kfs), len(mps)
+        S = np.zeros((max(nkf, 1), 12), np.float32)
+        if len(Scws) != nkf:
+            raise ValueError("FuseSim3Search takes one Scw per keyframe")
+        for k in range(nkf):
+            S[k] = np.asarray(Scws[k], np.float32).reshape(-1, 4)[:3].reshape(12)
+        ink = None
+        if in_kf is not None:
+            ink = np.ascontiguousarray(in_kf, np.uint8)
+            if ink.size != nkf * n:
+                raise ValueError("FuseSim3Search takes one in_kf flag per keyframe and point")
+        bi = np.full(max(nkf * n, 1), -1, np.int32)
+        bd = np.full(max(nkf * n, 1), 256, np.int32)
+        nf = np.zeros(max(nkf, 1), np.int32)
+        views = (FrameView * max(nkf, 1))()
+        for k in range(nkf):
+            views[k] = kfs[k].view()
+        check("orbmi_fuse_sim3_search_batch", lib().orbmi_fuse_sim3_search_batch(
+            self._h, nkf, C.addressof(views) if nkf else None, S.ctypes.data, mps.ctypes.data if n else None,
+            None if ink is None or not ink.size else ink.ctypes.data, n, float(th), bi.ctypes.data, bd.ctypes.data,
+            nf.ctypes.data))
+        return bi[:nkf * n].reshape(nkf, n), bd[:nkf * n].reshape(nkf, n), nf[:nkf]
 
     def SearchBySim3(self, kf1, mps1, has_mp1, kf2, mps2, has_mp2, match12, s12, R12, t12, th=7.5):
         """SearchBySim3(KeyFrame*, KeyFrame*, vector<MapPoint*>& vpMatches12, s12, R12, t12, th)

@@ -145,6 +145,7 @@ class KeyFrame:
     bad: bool = False
     fuse_target_for_kf: int = -1    # mnFuseTargetForKF
     tcp: np.ndarray = None          # mTcp (set when the keyframe turns bad)
+    loop_edges: list = dataclasses.field(default_factory=list)  # mspLoopEdges (loop.correct_loop adds them)
 
     @property
     def Ow(self) -> np.ndarray:
@@ -279,6 +280,8 @@ class MapPoint:
     found: int = 1                  # mnFound
     replaced: object = None         # mpReplaced
     fuse_candidate_for_kf: int = -1  # mnFuseCandidateForKF
+    corrected_by_kf: int = -1        # mnCorrectedByKF (loop.correct_loop)
+    corrected_reference: int = -1    # mnCorrectedReference
 
     def found_ratio(self) -> np.float32:
         """MapPoint::GetFoundRatio: static_cast<float>(mnFound) / mnVisible."""
