@@ -63,6 +63,15 @@ int orbmi_debug_greedy_cycles(unsigned long long* out, int reset);
  * permutation, every index a block reads in range). */
 int orbmi_debug_ba_schur_blocks(int nf, int* table, int cap, int* n_out);
 
+/* The launch plan of CreateNewMapPoints' device code (host computation, no GPU), from the
+ * functions the launchers and k_tri_match call themselves (csrc/tri_plan.h): for a first keyframe
+ * of kf1_n keypoints in fv1_nnodes vocabulary nodes searched against npairs >= 1 neighbours,
+ * out[0] = the slices every KF1 node is cut into; out[1] = the path of a KF2 node with
+ * kf2_node_size features (0 candidates in 2 registers per lane, 1 in 4, 2 read from memory);
+ * out[2] = the lanes per KF1 keypoint of the triangulation kernel (4 .. 64, 0 = the sequential
+ * kernel).  For the CPU test that the crafted scenes reach the paths they were built for. */
+int orbmi_debug_tri_plan(int kf1_n, int fv1_nnodes, int npairs, int kf2_node_size, int* out);
+
 /* The schedule of a run with the concurrent LocalMapping (orbmi_slam_settings.async_local_mapping):
  * one event per acquisition of the map lock, in acquisition order.  Tracking and LocalMapping
  * touch shared state (the map, the keyframe queue, AcceptKeyFrames) only while they hold it, and

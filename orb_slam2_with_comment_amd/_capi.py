@@ -116,6 +116,7 @@ _PROTOS = {
     "orbmi_ba_set_stop_at_check": (_i, [_vp, _i]),
     "orbmi_ba_set_enqueued_hook": (_i, [_vp, _vp, _vp]),
     "orbmi_debug_ba_schur_blocks": (_i, [_i, _vp, _i, _vp]),
+    "orbmi_debug_tri_plan": (_i, [_i, _i, _i, _i, _vp]),
     "orbmi_vocabulary_set_stream": (_i, [_vp, _vp]),
     "orbmi_fuse_search_refresh": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, C.c_float, _vp, _vp]),
     "orbmi_create_new_map_points": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,

@@ -42,6 +42,7 @@
 #include "matcher.h"
 #include "track_update.h"
 #include "tri_geom.h"
+#include "tri_plan.h"
 #include "wave_ops.h"
 
 namespace orbmi {
@@ -1622,16 +1623,19 @@ __device__ void tri_node_mem(const DevFrame& KF1, const uint8_t* __restrict__ ha
             const int dist = popc_desc(d1, KF2.desc + 32 * (long long)idx2);
             if (dist > TH_LOW) continue;
             const orbmi_keypoint kp2 = KF2.keys[idx2];
+            // the level table is indexed as tri_node_regs does: an octave outside it (not a legal
+            // input) reads the nearest entry, never past the table
+            const float sc2 = KF2.scale[min(max(kp2.octave, 0), kMaxLevels - 1)];
             if (!st1 && !st2) {
                 const float distex = T.ex - kp2.x;
                 const float distey = T.ey - kp2.y;
-                if (distex * distex + distey * distey < 100 * KF2.scale[kp2.octave]) continue;
+                if (distex * distex + distey * distey < 100 * sc2) continue;
             }
             const float num = la * kp2.x + lb * kp2.y + lc;
             const float den = la * la + lb * lb;
             if (den == 0) continue;
             const float dsqr = num * num / den;
-            const float sigma2 = KF2.scale[kp2.octave] * KF2.scale[kp2.octave];
+            const float sigma2 = sc2 * sc2;
             if (!((double)dsqr < 3.84 * (double)sigma2)) continue;
             const unsigned long long k = (unsigned long long)dist << 32 | (unsigned)(0xFFFFFFFFu - (unsigned)pos);
             key = k < key ? k : key;
@@ -1677,8 +1681,9 @@ __global__ __launch_bounds__(256) void k_tri_match(DevFrame KF1, const uint8_t* 
     const float invz = 1.0f / C2[2];
     T.ex = KF2.fx * C2[0] * invz + KF2.cx;
     T.ey = KF2.fy * C2[1] * invz + KF2.cy;
-    if (T.nf <= 128) tri_node_regs<2>(KF1, has_mp1, P, T, only_stereo, check_ori, lane);
-    else if (T.nf <= 256) tri_node_regs<4>(KF1, has_mp1, P, T, only_stereo, check_ori, lane);
+    const int path = tri_node_path(T.nf);
+    if (path == 0) tri_node_regs<2>(KF1, has_mp1, P, T, only_stereo, check_ori, lane);
+    else if (path == 1) tri_node_regs<4>(KF1, has_mp1, P, T, only_stereo, check_ori, lane);
     else tri_node_mem(KF1, has_mp1, P, T, only_stereo, check_ori, lane);
 }
 
@@ -1686,15 +1691,6 @@ __global__ __launch_bounds__(256) void k_tri_match(DevFrame KF1, const uint8_t* 
 __global__ __launch_bounds__(1024) void k_tri_finalize(int n1, const TriPair* __restrict__ pairs, int check_ori) {
     const TriPair& P = pairs[blockIdx.x];
     finalize_block(n1, check_ori, P.hist, P.bin_of, P.match, P.nmatches);
-}
-
-// slices per node: enough waves for the chip (~4096 over all pairs) while a slice keeps ~16 KF1
-// features to amortise loading the node's KF2 candidates
-static int tri_splits(const DevFrame& KF1, const DevFV& fv1, int npairs) {
-    const int nodes = std::max(fv1.nnodes, 1);
-    const int by_chip = 4096 / std::max(nodes * npairs, 1);
-    const int by_size = std::max(KF1.n / nodes / 16, 1);
-    return std::max(1, std::min(std::min(by_chip, by_size), 64));
 }
 
 // per-pair scratch and outputs of the search: match rows are consecutive (pair j at
@@ -1725,7 +1721,7 @@ static int launch_tri_search(Matcher& m, const DevFrame& KF1, const uint8_t* has
     if (check_ori) ORBMI_HIP(hipMemsetAsync(m.d_hist, 0, (size_t)HISTO_LENGTH * npairs * sizeof(int), m.ls()));
     if (KF1.n > 0) ORBMI_HIP(hipMemsetAsync(match, 0xFF, (size_t)KF1.n * npairs * sizeof(int), m.ls()));
     if (fv1.nnodes > 0) {
-        const int splits = tri_splits(KF1, fv1, npairs);
+        const int splits = tri_splits(KF1.n, fv1.nnodes, npairs);  // tri_plan.h
         const int waves = fv1.nnodes * splits;
         hipLaunchKernelGGL(k_tri_match, dim3((waves + 3) / 4, npairs), dim3(256), 0, m.ls(), KF1, has_mp1, fv1,
                            pairs_dev, only_stereo, check_ori, splits);
@@ -1831,20 +1827,17 @@ int launch_create_points(Matcher& m, const DevFrame& KF1, const uint8_t* has1, c
         hipLaunchKernelGGL(kern, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, m.ls(), S1, S2_dev, npairs, match,
                            KF1.n, ok, x3d);
     };
-    if (KF1.n <= 0) {
-    } else if (npairs <= 4) {
-        par(k_triangulate_par<4>, 4);
-    } else if (npairs <= 8) {
-        par(k_triangulate_par<8>, 8);
-    } else if (npairs <= 16) {
-        par(k_triangulate_par<16>, 16);
-    } else if (npairs <= 32) {
-        par(k_triangulate_par<32>, 32);
-    } else if (npairs <= 64) {
-        par(k_triangulate_par<64>, 64);
-    } else {
-        hipLaunchKernelGGL(k_triangulate, dim3((KF1.n + 255) / 256), dim3(256), 0, m.ls(), S1, S2_dev, npairs, match,
-                           KF1.n, ok, x3d);
+    if (KF1.n > 0) {
+        switch (tri_group_width(npairs)) {  // tri_plan.h
+            case 4: par(k_triangulate_par<4>, 4); break;
+            case 8: par(k_triangulate_par<8>, 8); break;
+            case 16: par(k_triangulate_par<16>, 16); break;
+            case 32: par(k_triangulate_par<32>, 32); break;
+            case 64: par(k_triangulate_par<64>, 64); break;
+            default:
+                hipLaunchKernelGGL(k_triangulate, dim3((KF1.n + 255) / 256), dim3(256), 0, m.ls(), S1, S2_dev, npairs,
+                                   match, KF1.n, ok, x3d);
+        }
     }
     return hipGetLastError() == hipSuccess ? ORBMI_OK : ORBMI_E_HIP;
 }
@@ -2264,3 +2257,11 @@ int launch_distinctive(Matcher& m, const uint8_t* desc, const int* off, int np, 
 }
 
 }  // namespace orbmi
+
+extern "C" int orbmi_debug_tri_plan(int kf1_n, int fv1_nnodes, int npairs, int kf2_node_size, int* out) {
+    if (!out || kf1_n < 0 || fv1_nnodes < 0 || npairs < 1 || kf2_node_size < 0) return ORBMI_E_ARG;
+    out[0] = orbmi::tri_splits(kf1_n, fv1_nnodes, npairs);
+    out[1] = orbmi::tri_node_path(kf2_node_size);
+    out[2] = orbmi::tri_group_width(npairs);
+    return ORBMI_OK;
+}
