@@ -88,11 +88,10 @@ __global__ __launch_bounds__(256) void k_bow_descend(VocDev v, const uint4* __re
 // order, cdesc) and a 4-step DPP min over (distance << 8 | child position) -- the lowest
 // position wins ties, as the reference's strict `d < best_d` scan does.
 __device__ inline unsigned row_min_u32(unsigned v) {
-    v = min(v, (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0xB1, 0xf, 0xf, false));   // xor 1
-    v = min(v, (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x4E, 0xf, 0xf, false));   // xor 2
-    v = min(v, (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x141, 0xf, 0xf, false));  // mirror 8
-    v = min(v, (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x128, 0xf, 0xf, false));  // ror 8
-    return v;
+    v = min(v, dpp_mov_u32<kDppXor1>(v));
+    v = min(v, dpp_mov_u32<kDppXor2>(v));
+    v = min(v, dpp_mov_u32<kDppHalfMirror>(v));
+    return min(v, dpp_mov_u32<kDppRor8>(v));
 }
 
 __global__ __launch_bounds__(256) void k_bow_descend16(VocDev v, const uint4* __restrict__ feats, int n,

@@ -201,6 +201,34 @@ int finish(Matcher& m, std::vector<OutBuf>& outs, int* nmatches_dev, int* nmatch
     return ORBMI_OK;
 }
 
+// finish() for the batched entries, whose counts are an array of n (user_counts == nullptr: not
+// asked for)
+int finish_counts(Matcher& m, std::vector<OutBuf>& outs, int* user_counts, const int* dev_counts, int n) {
+    bool wait = false;
+    ORBMI_HIP(m.flush_up());
+    if (m.up_err != hipSuccess) return ORBMI_E_HIP;
+    for (OutBuf& o : outs)
+        if (o.bytes) { ORBMI_HIP(m.d2h(o.user, o.dev, o.bytes)); wait = true; }
+    if (user_counts) {
+        ORBMI_HIP(m.d2h(user_counts, dev_counts, sizeof(int) * (size_t)n));
+        wait = true;
+    }
+    if (wait) ORBMI_HIP(hipStreamSynchronize(m.ls()));
+    m.d2h_flush();
+    return ORBMI_OK;
+}
+
+// Scw = [sRcw | t] into T = [Rcw | tcw] and the camera centre Ow (src/ORBmatcher.cc:368-374,
+// :1148-1153), float: scw = sqrt(row 0 . row 0) (the dot product in double, rounded to float),
+// Rcw = sRcw / scw, tcw = t / scw, Ow = -Rcw^T tcw.  Returns scw; what a degenerate one means is
+// the caller's business.
+float decompose_scw(const float* Scw, float T[12], float Ow[3]) {
+    const float scw = (float)sqrt(((double)Scw[0] * Scw[0] + (double)Scw[1] * Scw[1]) + (double)Scw[2] * Scw[2]);
+    for (int k = 0; k < 12; k++) T[k] = Scw[k] / scw;
+    for (int c = 0; c < 3; c++) Ow[c] = -((T[c] * T[3] + T[4 + c] * T[7]) + T[8 + c] * T[11]);
+    return scw;
+}
+
 int read_small(const float* p, int n, float* out) {
     if (on_device(p)) {
         ORBMI_HIP(hipMemcpy(out, p, n * sizeof(float), hipMemcpyDeviceToHost));
@@ -848,18 +876,7 @@ int orbmi_search_for_triangulation_batch(orbmi_matcher* h, const orbmi_frame_vie
     if ((rc = orbmi::launch_triangulation(m, K1, d_mp1, f1, npairs, pairs.data(), d_pairs, only_stereo, check_ori,
                                           d_out)))
         return rc;
-    bool wait = false;
-    ORBMI_HIP(m.flush_up());
-    if (m.up_err != hipSuccess) return ORBMI_E_HIP;
-    for (OutBuf& o : outs)
-        if (o.bytes) { ORBMI_HIP(m.d2h(o.user, o.dev, o.bytes)); wait = true; }
-    if (nmatches) {
-        ORBMI_HIP(m.d2h(nmatches, d_counts, (size_t)npairs * sizeof(int)));
-        wait = true;
-    }
-    if (wait) ORBMI_HIP(hipStreamSynchronize(m.ls()));
-    m.d2h_flush();
-    return ORBMI_OK;
+    return finish_counts(m, outs, nmatches, d_counts, npairs);
 }
 
 int orbmi_create_new_map_points(orbmi_matcher* h, const orbmi_frame_view* kf1, const orbmi_tri_keyframe* tri1,
@@ -922,18 +939,7 @@ int orbmi_fuse_search_batch(orbmi_matcher* h, int nkf, const orbmi_frame_view* k
     std::vector<OutBuf> outs;
     if ((rc = fuse_batch_stage(m, nkf, kfs, nullptr, mps, in_kf, n_mp, best_idx, best_dist, outs, &P))) return rc;
     if ((rc = fuse_batch_launch(m, P, th))) return rc;
-    bool wait = false;
-    ORBMI_HIP(m.flush_up());
-    if (m.up_err != hipSuccess) return ORBMI_E_HIP;
-    for (OutBuf& o : outs)
-        if (o.bytes) { ORBMI_HIP(m.d2h(o.user, o.dev, o.bytes)); wait = true; }
-    if (ncandidates) {
-        ORBMI_HIP(m.d2h(ncandidates, P.d_cnt, sizeof(int) * nkf));
-        wait = true;
-    }
-    if (wait) ORBMI_HIP(hipStreamSynchronize(m.ls()));
-    m.d2h_flush();
-    return ORBMI_OK;
+    return finish_counts(m, outs, ncandidates, P.d_cnt, nkf);
 }
 
 int orbmi_fuse_search_refresh(orbmi_matcher* h, const uint8_t* obs_desc, const int32_t* obs_off, int nd, int32_t* best,
@@ -1242,11 +1248,7 @@ int orbmi_search_by_projection_sim3(orbmi_matcher* h, const orbmi_frame_view* kf
     if ((rc = make_frame(m, kf, &F, false))) return rc;
     orbmi::ProjSim3Args a;
     memset(&a, 0, sizeof(a));
-    // Scw = [sRcw | t]: scw = sqrt(row 0 . row 0) (the dot product in double, rounded to float),
-    // Rcw = sRcw / scw, tcw = t / scw, Ow = -Rcw^T tcw (:368-374), float
-    const float scw = (float)sqrt(((double)Scw[0] * Scw[0] + (double)Scw[1] * Scw[1]) + (double)Scw[2] * Scw[2]);
-    for (int k = 0; k < 12; k++) a.T[k] = Scw[k] / scw;
-    for (int c = 0; c < 3; c++) a.Ow[c] = -((a.T[c] * a.T[3] + a.T[4 + c] * a.T[7]) + a.T[8 + c] * a.T[11]);
+    (void)decompose_scw(Scw, a.T, a.Ow);  // (no test of scw here: a degenerate Scw finds nothing)
     // spAlreadyFound and the occupied keypoints
     std::vector<uint8_t> skip((size_t)n, 0), occ((size_t)nk, 0);
     for (int k = 0; k < nk; k++) {
@@ -1310,17 +1312,11 @@ int orbmi_fuse_sim3_search_batch(orbmi_matcher* h, int nkf, const orbmi_frame_vi
     if (!h || nkf < 0 || n_mp < 0 || (nkf > 0 && (!kfs || !Scw || on_device(Scw))) ||
         (nkf > 0 && n_mp > 0 && (!mps || !best_idx || !best_dist)))
         return ORBMI_E_ARG;
-    // Scw = [sRcw | t] per keyframe: scw = sqrt(row 0 . row 0) (the dot product in double, rounded
-    // to float), Rcw = sRcw / scw, tcw = t / scw, Ow = -Rcw^T tcw (:1148-1153), float; once per
-    // keyframe, as orbmi_search_by_projection_sim3 does it
+    // one decomposed Scw per keyframe
     std::vector<orbmi::FuseSim3Pose> poses((size_t)nkf);
     for (int k = 0; k < nkf; k++) {
-        const float* S = Scw + 12 * (size_t)k;
-        orbmi::FuseSim3Pose& P = poses[k];
-        const float scw = (float)sqrt(((double)S[0] * S[0] + (double)S[1] * S[1]) + (double)S[2] * S[2]);
+        const float scw = decompose_scw(Scw + 12 * (size_t)k, poses[k].T, poses[k].Ow);
         if (!(scw > 0.0f) || !std::isfinite(scw)) return ORBMI_E_ARG;
-        for (int q = 0; q < 12; q++) P.T[q] = S[q] / scw;
-        for (int c = 0; c < 3; c++) P.Ow[c] = -((P.T[c] * P.T[3] + P.T[4 + c] * P.T[7]) + P.T[8 + c] * P.T[11]);
     }
     if (nkf == 0 || n_mp == 0) return ORBMI_OK;
     Matcher& m = h->m;
@@ -1348,18 +1344,7 @@ int orbmi_fuse_sim3_search_batch(orbmi_matcher* h, int nkf, const orbmi_frame_vi
     ORBMI_HIP(m.h2d(d_k, K.data(), sizeof(FuseKF) * nkf));
     ORBMI_HIP(m.h2d(d_p, poses.data(), sizeof(orbmi::FuseSim3Pose) * nkf));
     if ((rc = orbmi::launch_fuse_sim3(m, nkf, d_k, d_p, d_mps, n_mp, th, ncap))) return rc;
-    bool wait = false;
-    ORBMI_HIP(m.flush_up());
-    if (m.up_err != hipSuccess) return ORBMI_E_HIP;
-    for (OutBuf& o : outs)
-        if (o.bytes) { ORBMI_HIP(m.d2h(o.user, o.dev, o.bytes)); wait = true; }
-    if (nfused) {
-        ORBMI_HIP(m.d2h(nfused, d_cnt, sizeof(int) * nkf));
-        wait = true;
-    }
-    if (wait) ORBMI_HIP(hipStreamSynchronize(m.ls()));
-    m.d2h_flush();
-    return ORBMI_OK;
+    return finish_counts(m, outs, nfused, d_cnt, nkf);
 }
 
 namespace {

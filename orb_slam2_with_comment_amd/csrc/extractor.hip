@@ -1255,11 +1255,10 @@ __constant__ float4 c_pattern_f[256];     // (x0, x1, y0, y1) of pair t = 16 l +
 __constant__ uint4 c_ictab[4][kIcItems];  // {u + 16 weights, circle mask, window row, 4 * dword}
 
 __device__ inline unsigned row16_sum(unsigned v) {  // sum over the lane's DPP row, in every lane
-    using namespace wave_detail;
-    v += (unsigned)dpp<0xB1>((int)v);
-    v += (unsigned)dpp<0x4E>((int)v);
-    v += (unsigned)dpp<0x141>((int)v);
-    return v + (unsigned)dpp<0x128>((int)v);
+    v += dpp_mov_u32<kDppXor1>(v);
+    v += dpp_mov_u32<kDppXor2>(v);
+    v += dpp_mov_u32<kDppHalfMirror>(v);
+    return v + dpp_mov_u32<kDppRor8>(v);
 }
 
 __global__ __launch_bounds__(64 * kDescWaves) void k_describe4(const uint8_t* __restrict__ pyr,

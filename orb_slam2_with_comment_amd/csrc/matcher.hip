@@ -19,7 +19,7 @@
 //
 // One window walk (for_features_in_area<G>) serves all seven projection-guided searches: the
 // tracking pair and their greedy fallback through window_candidates; Fuse, both directions of
-// SearchBySim3 and SearchByProjection(KF, Scw) through the keyframe query (kf_project ...
+// SearchBySim3 and SearchByProjection(KF, Scw) through the keyframe query (kf_point ...
 // windowed_best; k_sim3_search writes two of its steps out, see there).  frustum_record and
 // lf_query keep Frame.cc's own projection (see there).
 //
@@ -138,6 +138,23 @@ __device__ inline unsigned long long cand_entry(int dist, int cell, int idx) {
     return ((unsigned long long)dist << 40) | ((unsigned long long)cell << 20) | (unsigned)idx;
 }
 
+// The two least keys seen (bestDist / bestDist2 of every search: the keys are distinct, one per
+// keypoint, so the second is the least once the best is excluded)
+struct Best2 {
+    unsigned long long b1 = ~0ull, b2 = ~0ull;
+    __device__ void take(unsigned long long e) {
+        if (e < b1) { b2 = b1; b1 = e; }
+        else if (e < b2) b2 = e;
+    }
+    // the two least keys over the lanes of the wave, in every lane
+    __device__ Best2 wave_merge() const {
+        Best2 m;
+        m.b1 = wave_min_u64(b1);
+        m.b2 = wave_min_u64(b1 == m.b1 ? b2 : b1);
+        return m;
+    }
+};
+
 // A tracking search's window: centre, radius (also the bound on the right-image coordinate ur),
 // GetFeaturesInArea's level limits and the query's descriptor
 struct Window {
@@ -172,9 +189,9 @@ __device__ inline void camera_center(const float* T, float* o) {
 
 // -------------------------------------------------------------------------- keyframe query
 // How a map point becomes a window in a keyframe: the steps that Fuse, SearchBySim3 and
-// SearchByProjection(KF, Scw) share, each in the one operation order of all three.  The validity
-// flags, the vector the distance is taken from, the gates on a keypoint and the outputs stay with
-// the callers.
+// SearchByProjection(KF, Scw) share, each in the one operation order of all three.  kf_point is
+// the whole head of the query for the searches that project with the keyframe's own intrinsics;
+// the validity flags, the gates on a keypoint and the outputs stay with the callers.
 
 // the pinhole projection of Pc (intrinsics passed in: SearchBySim3 projects with KF1's) and
 // KeyFrame::IsInImage of F
@@ -197,6 +214,33 @@ __device__ inline bool in_distance_range(const orbmi_mappoint& mp, float dist) {
 __device__ inline bool in_viewing_cone(const orbmi_mappoint& mp, const float* PO, float dist) {
     const double dot = (double)PO[0] * mp.normal[0] + (double)PO[1] * mp.normal[1] + (double)PO[2] * mp.normal[2];
     return !(dot < 0.5 * (double)dist);
+}
+
+// The head of the keyframe query, in the order of Fuse, Fuse(KF, Scw) and SearchByProjection(KF,
+// Scw): a point the caller still accepts (ok) goes through T = [Rcw | tcw], z < 0, the projection
+// with F's intrinsics and the distance and viewing-cone tests against the camera centre Ow
+// (center(buf) returns it, from a table or computed into buf; it is asked only once the projection
+// has passed).  Returns whether the point is a query; then (u, v), 1 / z and the distance are set,
+// else they are 0.  The frame comes by pointer: a reference parameter declares the whole frame
+// readable ahead of the tests, and the compiler then moves k_fuse_sim3's loads of it.
+template <class Center>
+__device__ inline bool kf_point(const DevFrame* F, const orbmi_mappoint& mp, bool ok, const float* T, Center center,
+                                float* u, float* v, float* invz, float* dist) {
+    float Pc[3] = {0, 0, 0};
+    *u = *v = *invz = *dist = 0;
+    if (ok) {
+        transform(T, mp.pos, Pc);
+        ok = !(Pc[2] < 0.0f);
+    }
+    if (ok) ok = kf_project(*F, F->fx, F->fy, F->cx, F->cy, Pc, u, v, invz);
+    if (ok) {
+        float buf[3];
+        const float* Ow = center(buf);
+        const float PO[3] = {mp.pos[0] - Ow[0], mp.pos[1] - Ow[1], mp.pos[2] - Ow[2]};
+        *dist = (float)sqrt((double)PO[0] * PO[0] + (double)PO[1] * PO[1] + (double)PO[2] * PO[2]);
+        ok = in_distance_range(mp, *dist) && in_viewing_cone(mp, PO, *dist);
+    }
+    return ok;
 }
 
 // MapPoint::PredictScale(dist, .) against F's pyramid
@@ -477,6 +521,8 @@ constexpr int kGreedyRounds = 48;
 // Result of query q under occupancy test occ(idx) (sequential semantics of one iteration).
 template <class Occ>
 __device__ inline int greedy_eval(const GreedyArgs& a, int q, const float* Tc, bool fw, bool bw, Occ occ) {
+    // (Best2 written out, here and in k_greedy's slow path: through the struct k_greedy's
+    // instruction stream changes, and the tracking chain is held to tools/asm_kernel_diff.py)
     unsigned long long b1 = ~0ull, b2 = ~0ull;
     auto take = [&](unsigned long long e) {
         if (occ((int)(e & 0xFFFFF))) return;
@@ -807,8 +853,8 @@ __global__ __launch_bounds__(kGreedyThreads) void k_greedy(GreedyArgs a) {
                         if (e < b1) { b2 = b1; b1 = e; }
                         else if (e < b2) b2 = e;
                     }
-                    const unsigned long long m1 = wave_min_u64_dpp(b1);
-                    const unsigned long long m2 = wave_min_u64_dpp(b1 == m1 ? b2 : b1);
+                    const unsigned long long m1 = wave_min_u64(b1);
+                    const unsigned long long m2 = wave_min_u64(b1 == m1 ? b2 : b1);
                     const int r = greedy_decide(a, oct, (int)(m1 >> 40), m1 == ~0ull ? -1 : (int)(m1 & 0xFFFFF),
                                                 (int)(m2 >> 40), m2 == ~0ull ? -1 : (int)(m2 & 0xFFFFF));
                     if (lane == src) nr[k] = r;
@@ -929,9 +975,9 @@ __global__ __launch_bounds__(kGreedyThreads) void k_greedy(GreedyArgs a) {
         // lower bin (the scan's strict comparisons), by three wave maxima of count << 8 | (255 - bin)
         const int s = lane < HISTO_LENGTH ? hist[lane] : 0;
         const unsigned key = s > 0 ? ((unsigned)s << 8) | (unsigned)(255 - lane) : 0u;
-        const unsigned k1 = wave_max_u32_dpp(key);
-        const unsigned k2 = wave_max_u32_dpp(key == k1 ? 0u : key);
-        const unsigned k3 = wave_max_u32_dpp(key == k1 || key == k2 ? 0u : key);
+        const unsigned k1 = wave_max_u32(key);
+        const unsigned k2 = wave_max_u32(key == k1 ? 0u : key);
+        const unsigned k3 = wave_max_u32(key == k1 || key == k2 ? 0u : key);
         const int max1 = (int)(k1 >> 8), max2 = (int)(k2 >> 8), max3 = (int)(k3 >> 8);
         int ind1 = k1 ? 255 - (int)(k1 & 255) : -1, ind2 = k2 ? 255 - (int)(k2 & 255) : -1;
         int ind3 = k3 ? 255 - (int)(k3 & 255) : -1;
@@ -1013,58 +1059,72 @@ __global__ __launch_bounds__(1024) void k_track_update(DevFrame F, int stage, co
 // Each node of the KF feature vector finds its partner node in F (merge-join of two sorted
 // id lists, :234-320); nodes are independent (a feature belongs to one node), the greedy
 // exclusion (:265-266) is sequential inside the node: one wave per node.
-__global__ __launch_bounds__(256) void k_bow_match(DevFrame KF, const uint8_t* __restrict__ kf_ok, DevFV kfv,
-                                                   DevFrame F, DevFV fv, float nnratio, int check_ori,
-                                                   int* __restrict__ match, int* __restrict__ bin_of,
-                                                   int* __restrict__ hist) {
+// The node body of both forms, side 1's node `a` against its partner node of side 2.
+// KfKf = false, SearchByBoW(KeyFrame*, Frame&) (:234-320): side 1 is the keyframe (ok1 = its
+// keypoint has a live map point), side 2 the frame; the output is indexed by the frame's keypoint
+// (match[idx2] = idx1, which also serves as the "already matched" record of side 2: matched2
+// unused) and acceptance is bestDist1 <= TH_LOW (:286).
+// KfKf = true, SearchByBoW(KeyFrame*, KeyFrame*, vpMatches12) (:635-768): both sides need a live
+// map point (ok1 gates the outer loop :671-675, ok2 the inner one beside vbMatched2 :687-693),
+// acceptance is the strict bestDist1 < TH_LOW (:711) and the output is indexed by KF1's keypoint
+// (match[idx1] = idx2).  vbMatched2 lives in `matched2` (one int per KF2 keypoint, zeroed by the
+// launcher).
+// Both: rot = angle1 - angle2, the histogram holds the output's index, and for the first 64 * kPer
+// features of the node the "already matched" state lives in registers; features past that window
+// re-read it.
+template <bool KfKf>
+__device__ inline void bow_node_match(const DevFrame& KF1, const uint8_t* __restrict__ ok1, const DevFV& fv1,
+                                      const DevFrame& KF2, const uint8_t* __restrict__ ok2, const DevFV& fv2,
+                                      float nnratio, int check_ori, int* __restrict__ match,
+                                      int* __restrict__ matched2, int* __restrict__ bin_of, int* __restrict__ hist) {
     const int wid = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int a = blockIdx.x * 4 + wid;
-    if (a >= kfv.nnodes) return;
-    const unsigned id = kfv.node_id[a];
-    int lo = 0, hi = fv.nnodes;  // lower_bound
-    while (lo < hi) { const int mid = (lo + hi) >> 1; if (fv.node_id[mid] < id) lo = mid + 1; else hi = mid; }
-    if (lo >= fv.nnodes || fv.node_id[lo] != id) return;
-    const int f0 = fv.off[lo], nf = fv.off[lo + 1] - f0;
-    constexpr int kPer = 8;  // F features per lane kept in registers
+    if (a >= fv1.nnodes) return;
+    const unsigned id = fv1.node_id[a];
+    int lo = 0, hi = fv2.nnodes;  // lower_bound
+    while (lo < hi) { const int mid = (lo + hi) >> 1; if (fv2.node_id[mid] < id) lo = mid + 1; else hi = mid; }
+    if (lo >= fv2.nnodes || fv2.node_id[lo] != id) return;
+    const int f0 = fv2.off[lo], nf = fv2.off[lo + 1] - f0;
+    constexpr int kPer = 8;  // side 2 features per lane kept in registers
     bool matched[kPer];
 #pragma unroll
     for (int k = 0; k < kPer; k++) matched[k] = false;
-    for (int ia = kfv.off[a]; ia < kfv.off[a + 1]; ia++) {
-        const int realIdxKF = kfv.feat[ia];
-        if (!kf_ok[realIdxKF]) continue;
-        const uint8_t* dKF = KF.desc + 32 * (long long)realIdxKF;
-        unsigned long long b1 = ~0ull, b2 = ~0ull;
+    for (int ia = fv1.off[a]; ia < fv1.off[a + 1]; ia++) {
+        const int idx1 = fv1.feat[ia];
+        if ((KfKf && (unsigned)idx1 >= (unsigned)KF1.n) || !ok1[idx1]) continue;
+        const uint8_t* d1 = KF1.desc + 32 * (long long)idx1;
+        Best2 b;
         for (int base = 0; base < nf; base += 64 * kPer) {
 #pragma unroll
             for (int k = 0; k < kPer; k++) {
                 const int pos = base + k * 64 + lane;
                 if (pos >= nf) continue;
-                const int realIdxF = fv.feat[f0 + pos];
-                const bool done = base == 0 ? matched[k] : match[realIdxF] >= 0;
+                const int idx2 = fv2.feat[f0 + pos];
+                if (KfKf && ((unsigned)idx2 >= (unsigned)KF2.n || !ok2[idx2])) continue;
+                const bool done = base == 0 ? matched[k] : KfKf ? matched2[idx2] != 0 : match[idx2] >= 0;
                 if (done) continue;
-                const unsigned long long e = ((unsigned long long)popc_desc(dKF, F.desc + 32 * (long long)realIdxF) << 32) | (unsigned)pos;
-                if (e < b1) { b2 = b1; b1 = e; } else if (e < b2) b2 = e;
+                b.take(((unsigned long long)popc_desc(d1, KF2.desc + 32 * (long long)idx2) << 32) | (unsigned)pos);
             }
         }
-        // wave-wide best / second best of the (dist, position) keys
-        const unsigned long long m1 = wave_min_u64(b1);
-        const unsigned long long c2 = b1 == m1 ? b2 : b1;
-        const unsigned long long m2 = wave_min_u64(c2);
-        const int bestDist1 = m1 == ~0ull ? 256 : (int)(m1 >> 32);
-        const int bestDist2 = m2 == ~0ull ? 256 : (int)(m2 >> 32);
-        if (bestDist1 <= TH_LOW && (float)bestDist1 < nnratio * (float)bestDist2) {
-            const int pos = (int)(m1 & 0xFFFFFFFFu);
-            const int realIdxF = fv.feat[f0 + pos];
+        // (dist, position) keys: the least one is the first feature in node order at bestDist1
+        const Best2 w = b.wave_merge();
+        const int bestDist1 = w.b1 == ~0ull ? 256 : (int)(w.b1 >> 32);
+        const int bestDist2 = w.b2 == ~0ull ? 256 : (int)(w.b2 >> 32);
+        if ((KfKf ? bestDist1 < TH_LOW : bestDist1 <= TH_LOW) && (float)bestDist1 < nnratio * (float)bestDist2) {
+            const int pos = (int)(w.b1 & 0xFFFFFFFFu);
+            const int idx2 = fv2.feat[f0 + pos];
             if (pos < 64 * kPer && lane == (pos & 63)) {
 #pragma unroll
                 for (int k = 0; k < kPer; k++)
                     if (k == (pos >> 6)) matched[k] = true;
             }
             if (lane == 0) {
-                match[realIdxF] = realIdxKF;
+                const int out = KfKf ? idx1 : idx2;
+                match[out] = KfKf ? idx2 : idx1;
+                if (KfKf) matched2[idx2] = 1;
                 if (check_ori) {
-                    const int bin = rot_bin(KF.keys[realIdxKF].angle, F.keys[realIdxF].angle);
-                    bin_of[realIdxF] = bin;
+                    const int bin = rot_bin(KF1.keys[idx1].angle, KF2.keys[idx2].angle);
+                    bin_of[out] = bin;
                     atomicAdd(&hist[bin], 1);
                 }
             }
@@ -1074,75 +1134,19 @@ __global__ __launch_bounds__(256) void k_bow_match(DevFrame KF, const uint8_t* _
     }
 }
 
-// SearchByBoW(KeyFrame*, KeyFrame*, vpMatches12) (src/ORBmatcher.cc:635-768), the sibling of
-// k_bow_match: one wave per KF1 node.  What differs from the (KF, Frame) form: both sides need a
-// live map point (ok1 gates the outer loop :671-675, ok2 the inner one beside vbMatched2
-// :687-693), acceptance is the strict bestDist1 < TH_LOW (:711), the output is indexed by KF1's
-// keypoint (match12[idx1] = idx2), rot = angle1 - angle2 and the histogram holds idx1.
-// vbMatched2 lives in `matched2` (one int per KF2 keypoint, zeroed by the launcher) and, for the
-// first 64 * kPer features of the node, in registers; features past that window re-read it.
+__global__ __launch_bounds__(256) void k_bow_match(DevFrame KF, const uint8_t* __restrict__ kf_ok, DevFV kfv,
+                                                   DevFrame F, DevFV fv, float nnratio, int check_ori,
+                                                   int* __restrict__ match, int* __restrict__ bin_of,
+                                                   int* __restrict__ hist) {
+    bow_node_match<false>(KF, kf_ok, kfv, F, nullptr, fv, nnratio, check_ori, match, nullptr, bin_of, hist);
+}
+
 __global__ __launch_bounds__(256) void k_bow_match_kf(DevFrame KF1, const uint8_t* __restrict__ ok1, DevFV fv1,
                                                       DevFrame KF2, const uint8_t* __restrict__ ok2, DevFV fv2,
                                                       float nnratio, int check_ori, int* __restrict__ match12,
                                                       int* __restrict__ matched2, int* __restrict__ bin_of,
                                                       int* __restrict__ hist) {
-    const int wid = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int a = blockIdx.x * 4 + wid;
-    if (a >= fv1.nnodes) return;
-    const unsigned id = fv1.node_id[a];
-    int lo = 0, hi = fv2.nnodes;  // lower_bound
-    while (lo < hi) { const int mid = (lo + hi) >> 1; if (fv2.node_id[mid] < id) lo = mid + 1; else hi = mid; }
-    if (lo >= fv2.nnodes || fv2.node_id[lo] != id) return;
-    const int f0 = fv2.off[lo], nf = fv2.off[lo + 1] - f0;
-    constexpr int kPer = 8;  // KF2 features per lane kept in registers
-    bool matched[kPer];
-#pragma unroll
-    for (int k = 0; k < kPer; k++) matched[k] = false;
-    for (int ia = fv1.off[a]; ia < fv1.off[a + 1]; ia++) {
-        const int idx1 = fv1.feat[ia];
-        if ((unsigned)idx1 >= (unsigned)KF1.n || !ok1[idx1]) continue;
-        const uint8_t* d1 = KF1.desc + 32 * (long long)idx1;
-        unsigned long long b1 = ~0ull, b2 = ~0ull;
-        for (int base = 0; base < nf; base += 64 * kPer) {
-#pragma unroll
-            for (int k = 0; k < kPer; k++) {
-                const int pos = base + k * 64 + lane;
-                if (pos >= nf) continue;
-                const int idx2 = fv2.feat[f0 + pos];
-                if ((unsigned)idx2 >= (unsigned)KF2.n || !ok2[idx2]) continue;
-                const bool done = base == 0 ? matched[k] : matched2[idx2] != 0;
-                if (done) continue;
-                const unsigned long long e = ((unsigned long long)popc_desc(d1, KF2.desc + 32 * (long long)idx2) << 32) | (unsigned)pos;
-                if (e < b1) { b2 = b1; b1 = e; } else if (e < b2) b2 = e;
-            }
-        }
-        // (dist, position) keys: the least one is the first feature in node order at bestDist1
-        const unsigned long long m1 = wave_min_u64(b1);
-        const unsigned long long c2 = b1 == m1 ? b2 : b1;
-        const unsigned long long m2 = wave_min_u64(c2);
-        const int bestDist1 = m1 == ~0ull ? 256 : (int)(m1 >> 32);
-        const int bestDist2 = m2 == ~0ull ? 256 : (int)(m2 >> 32);
-        if (bestDist1 < TH_LOW && (float)bestDist1 < nnratio * (float)bestDist2) {
-            const int pos = (int)(m1 & 0xFFFFFFFFu);
-            const int idx2 = fv2.feat[f0 + pos];
-            if (pos < 64 * kPer && lane == (pos & 63)) {
-#pragma unroll
-                for (int k = 0; k < kPer; k++)
-                    if (k == (pos >> 6)) matched[k] = true;
-            }
-            if (lane == 0) {
-                match12[idx1] = idx2;
-                matched2[idx2] = 1;
-                if (check_ori) {
-                    const int bin = rot_bin(KF1.keys[idx1].angle, KF2.keys[idx2].angle);
-                    bin_of[idx1] = bin;
-                    atomicAdd(&hist[bin], 1);
-                }
-            }
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-        }
-    }
+    bow_node_match<true>(KF1, ok1, fv1, KF2, ok2, fv2, nnratio, check_ori, match12, matched2, bin_of, hist);
 }
 
 // rotation-histogram filter (ComputeThreeMaxima, src/ORBmatcher.cc:1854-1895) of one search's
@@ -1209,7 +1213,7 @@ __global__ __launch_bounds__(256) void k_xmatch_partial(const uint8_t* __restric
         const uint4* p = reinterpret_cast<const uint4*>(qd + 32 * (long long)q);
         a0 = p[0]; a1 = p[1];
     }
-    unsigned long long b1 = ~0ull, b2 = ~0ull;
+    Best2 b;
     for (int base = t0; base < t1; base += kXChunk) {
         const int nt = min(kXChunk, t1 - base);
         __syncthreads();
@@ -1219,22 +1223,17 @@ __global__ __launch_bounds__(256) void k_xmatch_partial(const uint8_t* __restric
         for (int k = w; k < nt; k += 4) {
             const int row = base + k, seg = row / seg_cap;
             if (seg == skip_seg || row - seg * seg_cap >= seg_counts[seg]) continue;
-            const unsigned long long e = ((unsigned long long)popc256(a0, a1, tile[2 * k], tile[2 * k + 1]) << 32) |
-                                         (unsigned)row;
-            if (e < b1) { b2 = b1; b1 = e; } else if (e < b2) b2 = e;
+            b.take(((unsigned long long)popc256(a0, a1, tile[2 * k], tile[2 * k + 1]) << 32) | (unsigned)row);
         }
     }
-    red[w][lane][0] = b1;
-    red[w][lane][1] = b2;
+    red[w][lane][0] = b.b1;
+    red[w][lane][1] = b.b2;
     __syncthreads();
     if (w == 0 && q < nq) {
         for (int o = 1; o < 4; o++)
-            for (int j = 0; j < 2; j++) {
-                const unsigned long long e = red[o][lane][j];
-                if (e < b1) { b2 = b1; b1 = e; } else if (e < b2) b2 = e;
-            }
-        part[((long long)blockIdx.y * nq_cap + q) * 2] = b1;
-        part[((long long)blockIdx.y * nq_cap + q) * 2 + 1] = b2;
+            for (int j = 0; j < 2; j++) b.take(red[o][lane][j]);
+        part[((long long)blockIdx.y * nq_cap + q) * 2] = b.b1;
+        part[((long long)blockIdx.y * nq_cap + q) * 2 + 1] = b.b2;
     }
 }
 
@@ -1245,16 +1244,13 @@ __global__ __launch_bounds__(256) void k_xmatch_final(int nq_cap, const int* __r
     const int q = blockIdx.x * blockDim.x + threadIdx.x;
     const int nq = nq_dev ? min(*nq_dev, nq_cap) : nq_cap;
     if (q >= nq) return;
-    unsigned long long b1 = ~0ull, b2 = ~0ull;
+    Best2 b;
     for (int s = 0; s < nsplit; s++)
-        for (int j = 0; j < 2; j++) {
-            const unsigned long long e = part[((long long)s * nq_cap + q) * 2 + j];
-            if (e < b1) { b2 = b1; b1 = e; } else if (e < b2) b2 = e;
-        }
+        for (int j = 0; j < 2; j++) b.take(part[((long long)s * nq_cap + q) * 2 + j]);
     int r = -1;
-    if (b1 != ~0ull) {
-        const int d1 = (int)(b1 >> 32), d2 = b2 == ~0ull ? 256 : (int)(b2 >> 32);
-        if (d1 <= th && (float)d1 < ratio * (float)d2) r = (int)(b1 & 0xFFFFFFFFu);
+    if (b.b1 != ~0ull) {
+        const int d1 = (int)(b.b1 >> 32), d2 = b.b2 == ~0ull ? 256 : (int)(b.b2 >> 32);
+        if (d1 <= th && (float)d1 < ratio * (float)d2) r = (int)(b.b1 & 0xFFFFFFFFu);
     }
     match[q] = r;
     if (r >= 0) atomicAdd(nmatches, 1);
@@ -1431,36 +1427,41 @@ int launch_track_update(Matcher& m, const DevFrame& F, int stage, const uint8_t*
     return ORBMI_OK;
 }
 
-int launch_bow(Matcher& m, const DevFrame& KF, const uint8_t* kf_ok, const DevFV& kfv, const DevFrame& F,
-               const DevFV& fv, float nnratio, int check_ori, int* match, int* nmatches) {
+// both SearchByBoW forms: matched2 != nullptr is the (KF, KF) form, whose output `match` is
+// indexed by side 1's keypoints; the (KF, Frame) form's by side 2's (the frame's)
+static int launch_bow_search(Matcher& m, const DevFrame& KF1, const uint8_t* ok1, const DevFV& fv1, const DevFrame& KF2,
+                             const uint8_t* ok2, const DevFV& fv2, float nnratio, int check_ori, int* match,
+                             int* matched2, int* nmatches) {
+    const DevFrame& O = matched2 ? KF1 : KF2;  // the frame whose keypoints index the output
     int rc;
-    if ((rc = ensure_buf(&m.d_bin_of, &m.cap_bin_of, (size_t)std::max(F.n, 1)))) return rc;
+    if ((rc = ensure_buf(&m.d_bin_of, &m.cap_bin_of, (size_t)std::max(O.n, 1)))) return rc;
     if ((rc = ensure_buf(&m.d_hist, &m.cap_hist, (size_t)HISTO_LENGTH))) return rc;
     ORBMI_HIP(hipMemsetAsync(m.d_hist, 0, HISTO_LENGTH * sizeof(int), m.ls()));
-    ORBMI_HIP(hipMemsetAsync(match, 0xFF, (size_t)std::max(F.n, 1) * sizeof(int), m.ls()));
-    if (kfv.nnodes > 0)
-        hipLaunchKernelGGL(k_bow_match, dim3((kfv.nnodes + 3) / 4), dim3(256), 0, m.ls(), KF, kf_ok, kfv, F, fv,
-                           nnratio, check_ori, match, m.d_bin_of, m.d_hist);
-    hipLaunchKernelGGL(k_bow_finalize, dim3(1), dim3(1024), 0, m.ls(), F, check_ori, m.d_hist, m.d_bin_of, match,
+    ORBMI_HIP(hipMemsetAsync(match, 0xFF, (size_t)std::max(O.n, 1) * sizeof(int), m.ls()));
+    const dim3 grid((fv1.nnodes + 3) / 4), block(256);
+    if (matched2) {
+        ORBMI_HIP(hipMemsetAsync(matched2, 0, (size_t)std::max(KF2.n, 1) * sizeof(int), m.ls()));
+        if (fv1.nnodes > 0 && fv2.nnodes > 0)
+            hipLaunchKernelGGL(k_bow_match_kf, grid, block, 0, m.ls(), KF1, ok1, fv1, KF2, ok2, fv2, nnratio, check_ori,
+                               match, matched2, m.d_bin_of, m.d_hist);
+    } else if (fv1.nnodes > 0) {
+        hipLaunchKernelGGL(k_bow_match, grid, block, 0, m.ls(), KF1, ok1, fv1, KF2, fv2, nnratio, check_ori, match,
+                           m.d_bin_of, m.d_hist);
+    }
+    hipLaunchKernelGGL(k_bow_finalize, dim3(1), dim3(1024), 0, m.ls(), O, check_ori, m.d_hist, m.d_bin_of, match,
                        nmatches);
     return ORBMI_OK;
+}
+
+int launch_bow(Matcher& m, const DevFrame& KF, const uint8_t* kf_ok, const DevFV& kfv, const DevFrame& F,
+               const DevFV& fv, float nnratio, int check_ori, int* match, int* nmatches) {
+    return launch_bow_search(m, KF, kf_ok, kfv, F, nullptr, fv, nnratio, check_ori, match, nullptr, nmatches);
 }
 
 int launch_bow_kf(Matcher& m, const DevFrame& KF1, const uint8_t* ok1, const DevFV& fv1, const DevFrame& KF2,
                   const uint8_t* ok2, const DevFV& fv2, float nnratio, int check_ori, int* match12, int* matched2,
                   int* nmatches) {
-    int rc;
-    if ((rc = ensure_buf(&m.d_bin_of, &m.cap_bin_of, (size_t)std::max(KF1.n, 1)))) return rc;
-    if ((rc = ensure_buf(&m.d_hist, &m.cap_hist, (size_t)HISTO_LENGTH))) return rc;
-    ORBMI_HIP(hipMemsetAsync(m.d_hist, 0, HISTO_LENGTH * sizeof(int), m.ls()));
-    ORBMI_HIP(hipMemsetAsync(match12, 0xFF, (size_t)std::max(KF1.n, 1) * sizeof(int), m.ls()));
-    ORBMI_HIP(hipMemsetAsync(matched2, 0, (size_t)std::max(KF2.n, 1) * sizeof(int), m.ls()));
-    if (fv1.nnodes > 0 && fv2.nnodes > 0)
-        hipLaunchKernelGGL(k_bow_match_kf, dim3((fv1.nnodes + 3) / 4), dim3(256), 0, m.ls(), KF1, ok1, fv1, KF2, ok2,
-                           fv2, nnratio, check_ori, match12, matched2, m.d_bin_of, m.d_hist);
-    hipLaunchKernelGGL(k_bow_finalize, dim3(1), dim3(1024), 0, m.ls(), KF1, check_ori, m.d_hist, m.d_bin_of, match12,
-                       nmatches);
-    return ORBMI_OK;
+    return launch_bow_search(m, KF1, ok1, fv1, KF2, ok2, fv2, nnratio, check_ori, match12, matched2, nmatches);
 }
 
 // ------------------------------------------------------------- SearchForTriangulation
@@ -1584,7 +1585,7 @@ __device__ void tri_node_regs(const DevFrame& KF1, const uint8_t* __restrict__ h
                     (unsigned long long)dist << 32 | (unsigned)(0xFFFFFFFFu - (unsigned)(lane + 64 * h));
                 if (pass && k < key) key = k;
             }
-            key = wave_min_u64_dpp(key);
+            key = wave_min_u64(key);
             if (key != ~0ull) {
                 const int pos = __builtin_amdgcn_readfirstlane((int)(0xFFFFFFFFu - (unsigned)(key & 0xFFFFFFFFu)));
                 int i2 = 0;
@@ -1863,21 +1864,10 @@ __device__ inline void fuse_one(const DevFrame& F, const int* __restrict__ cs, c
     int bi = -1, bd = 256;
     const orbmi_mappoint mp = mps[valid ? i : 0];
     const Pose34 T = frame_pose(F);
-    float Pc[3];
-    bool ok = valid && !(mp.flags & ORBMI_MP_BAD) && !(in_kf && in_kf[i]);
-    if (ok) {
-        transform(T.m, mp.pos, Pc);
-        ok = !(Pc[2] < 0.0f);
-    }
-    float u = 0, v = 0, invz = 0, dist3D = 0;
-    if (ok) ok = kf_project(F, F.fx, F.fy, F.cx, F.cy, Pc, &u, &v, &invz);
-    if (ok) {
-        float Ow[3];
-        camera_center(T.m, Ow);
-        const float PO[3] = {mp.pos[0] - Ow[0], mp.pos[1] - Ow[1], mp.pos[2] - Ow[2]};
-        dist3D = (float)sqrt((double)PO[0] * PO[0] + (double)PO[1] * PO[1] + (double)PO[2] * PO[2]);
-        ok = in_distance_range(mp, dist3D) && in_viewing_cone(mp, PO, dist3D);
-    }
+    float u, v, invz, dist3D;
+    const bool ok = kf_point(
+        &F, mp, valid && !(mp.flags & ORBMI_MP_BAD) && !(in_kf && in_kf[i]), T.m,
+        [&](float* buf) { camera_center(T.m, buf); return (const float*)buf; }, &u, &v, &invz, &dist3D);
     // the chi2 gates on the reprojection error (:1066-1089)
     const auto chi2_ok = [&](int idx, const orbmi_keypoint& kp) {
         const float inv = 1.0f / (F.scale[kp.octave] * F.scale[kp.octave]);  // mvInvLevelSigma2
@@ -1999,19 +1989,9 @@ __global__ __launch_bounds__(256) void k_fuse_sim3(const FuseKF* __restrict__ kf
     const DevFrame& F = K.F;
     const bool valid = i < n;  // the other lanes only take part in the group minimum
     const orbmi_mappoint mp = mps[valid ? i : 0];
-    bool ok = valid && !(mp.flags & ORBMI_MP_BAD) && !(K.in_kf && K.in_kf[i]);
-    float Pc[3] = {0, 0, 0};
-    if (ok) {
-        transform(P.T, mp.pos, Pc);
-        ok = !(Pc[2] < 0.0f);
-    }
-    float u = 0, v = 0, invz = 0, dist3D = 0;
-    if (ok) ok = kf_project(F, F.fx, F.fy, F.cx, F.cy, Pc, &u, &v, &invz);
-    if (ok) {
-        const float PO[3] = {mp.pos[0] - P.Ow[0], mp.pos[1] - P.Ow[1], mp.pos[2] - P.Ow[2]};
-        dist3D = (float)sqrt((double)PO[0] * PO[0] + (double)PO[1] * PO[1] + (double)PO[2] * PO[2]);
-        ok = in_distance_range(mp, dist3D) && in_viewing_cone(mp, PO, dist3D);
-    }
+    float u, v, invz, dist3D;
+    const bool ok = kf_point(&F, mp, valid && !(mp.flags & ORBMI_MP_BAD) && !(K.in_kf && K.in_kf[i]), P.T,
+                             [&](float*) { return P.Ow; }, &u, &v, &invz, &dist3D);
     const unsigned long long best =
         windowed_best<kFuseLanes>(F, K.cs, K.cl, mp, ok, u, v, dist3D, th, glane,
                                   [](int, const orbmi_keypoint&) { return true; }, [](int, unsigned long long) {});
@@ -2158,19 +2138,9 @@ __global__ __launch_bounds__(256) void k_proj_sim3(DevFrame F, const int* __rest
     const bool valid = j < a.n;  // the other lanes only take part in the group minimum
     const int i = a.first + (valid ? j : 0);
     const orbmi_mappoint mp = a.mps[i];
-    bool ok = valid && !(mp.flags & ORBMI_MP_BAD) && !a.skip[i];
-    float Pc[3] = {0, 0, 0};
-    if (ok) {
-        transform(a.T, mp.pos, Pc);
-        ok = !(Pc[2] < 0.0f);
-    }
-    float u = 0, v = 0, invz = 0, dist3D = 0;
-    if (ok) ok = kf_project(F, F.fx, F.fy, F.cx, F.cy, Pc, &u, &v, &invz);
-    if (ok) {
-        const float PO[3] = {mp.pos[0] - a.Ow[0], mp.pos[1] - a.Ow[1], mp.pos[2] - a.Ow[2]};
-        dist3D = (float)sqrt((double)PO[0] * PO[0] + (double)PO[1] * PO[1] + (double)PO[2] * PO[2]);
-        ok = in_distance_range(mp, dist3D) && in_viewing_cone(mp, PO, dist3D);
-    }
+    float u, v, invz, dist3D;
+    const bool ok = kf_point(&F, mp, valid && !(mp.flags & ORBMI_MP_BAD) && !a.skip[i], a.T,
+                             [&](float*) { return a.Ow; }, &u, &v, &invz, &dist3D);
     const unsigned long long best = windowed_best<kFuseLanes>(
         F, cs, cl, mp, ok, u, v, dist3D, a.th, glane,
         [&](int idx, const orbmi_keypoint&) { return !a.occ[idx]; },
