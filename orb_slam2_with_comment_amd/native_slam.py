@@ -1,4 +1,4 @@
-"""System::TrackStereo on the native host loop (csrc/slam.cpp, orbmi_slam_* in include/orbmi.h):
+"""System::TrackStereo on the native host loop (csrc/slam.h and its units, orbmi_slam_* in include/orbmi.h):
 the map, Tracking and the synchronous LocalMapping in C++ around the MI355X operators, with the
 Python interface of system.StereoSLAM (TrackStereo, per-frame stats, trajectory writers) so the
 two can be compared frame by frame.  system.StereoSLAM stays the readable form of the same host

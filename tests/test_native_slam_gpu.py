@@ -1,4 +1,4 @@
-"""The native stereo SLAM host loop (csrc/slam.cpp, orbmi_slam_*) on MI355X against the same
+"""The native stereo SLAM host loop (csrc/slam.h and its units, orbmi_slam_*) on MI355X against the same
 host logic driven by the CPU oracle (system.StereoSLAM + tests/slam_backends.OracleBackend):
 config 1's 200-frame KITTI-shaped sequence gives identical per-frame Tracking
 decisions and the identical trajectory; the writers produce the reference's formats."""

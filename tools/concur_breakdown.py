@@ -1,5 +1,5 @@
 """Where the concurrent LocalMapping's accuracy goes when frames come back to back
-(VERDICT r04 item 2): the native loop (csrc/slam.cpp, LocalMapping on its own thread) on the
+(VERDICT r04 item 2): the native loop (csrc/slam_mapping.cpp, LocalMapping on its own thread) on the
 200-frame sequence of tests/test_native_slam_gpu.py, several runs per regime:
 
   back-to-back              the throughput regime (bench --mode system)
