@@ -272,7 +272,26 @@ def local_ba(problem, stop=False, edge_chi2=False, stop_at_check=-1):
     return out
 
 
-def pose_optimization(frames, obs, diag=False):
+TRIAL_DTYPE = np.dtype([("round", "<f8"), ("iteration", "<f8"), ("accepted", "<f8"), ("ok2", "<f8"), ("rel", "<f8")])
+_TRIAL_CAP = 4 * 10 * 10  # rounds x iterations x trials per iteration
+
+
+def _trials_on(L):
+    L.orc_pose_set_trials.argtypes = [C.c_void_p, C.c_int]
+    L.orc_pose_trial_count.restype = C.c_int
+    buf = np.zeros(_TRIAL_CAP, TRIAL_DTYPE)
+    L.orc_pose_set_trials(buf.ctypes.data, _TRIAL_CAP)
+    return buf
+
+
+def _trials_off(L, buf):
+    n = L.orc_pose_trial_count()
+    L.orc_pose_set_trials(None, 0)
+    assert 0 <= n <= _TRIAL_CAP, n
+    return buf[:n].copy()
+
+
+def pose_optimization(frames, obs, diag=False, trials=False):
     """Optimizer::PoseOptimization restatement over POSE_FRAME_DTYPE frames (updated in place:
     tcw, inliers, iterations) and POSE_OBS_DTYPE observations -> outlier flags (bool, per obs).
     diag=True also returns, per observation, the float chi2 it was classified with in each of
@@ -288,26 +307,29 @@ def pose_optimization(frames, obs, diag=False):
     out = np.zeros(len(obs), np.uint8)
     chi2 = np.full((4, len(obs)), np.nan, np.float32)
     stop = np.full((len(frames), 8), np.inf)
+    rec = []
     for f in range(len(frames)):
         n = int(frames[f]["n_obs"])
         b = int(frames[f]["obs_begin"])
         buf = np.full(4 * max(n, 1), np.nan, np.float32)
         if diag:
             L.orc_pose_set_diag(buf.ctypes.data, stop[f].ctypes.data)
+        tb = _trials_on(L) if trials else None
         L.orc_pose_optimization(frames[f:f + 1].ctypes.data, obs.ctypes.data, out.ctypes.data)
         L.orc_pose_set_diag(None, None)
+        if trials:
+            rec.append(_trials_off(L, tb))
         chi2[:, b:b + n] = buf[:4 * n].reshape(4, n)
-    if diag:
-        return out.astype(bool), chi2, stop
-    return out.astype(bool)
+    res = (out.astype(bool),) + ((chi2, stop) if diag else ()) + ((rec,) if trials else ())
+    return res if len(res) > 1 else res[0]
 
 
 def pose_optimization_frame(frame, inv_level_sigma2, match_lf=None, lf_points=None, match_mp=None, mps=None,
-                            diag=False):
+                            diag=False, trials=False):
     """Optimizer::PoseOptimization(Frame*) with edge assembly (oracle/track_oracle.cpp) ->
     (POSE_FRAME_DTYPE record, per-keypoint outlier flags); diag=True adds the per-round
     classification chi2 by keypoint (4 x n, NaN without an edge) and the 8 margins of
-    pose_optimization."""
+    pose_optimization; trials=True appends the frame's trial record (pose_optimization)."""
     from orb_slam2_with_comment_amd.types import POSE_FRAME_DTYPE
     L = lib()
     L.orc_pose_optimization_frame.argtypes = [C.c_void_p] * 5
@@ -322,11 +344,11 @@ def pose_optimization_frame(frame, inv_level_sigma2, match_lf=None, lf_points=No
     v = frame.view()
     if diag:
         L.orc_pose_set_frame_diag(chi2.ctypes.data, nk, stop.ctypes.data)
+    tb = _trials_on(L) if trials else None
     L.orc_pose_optimization_frame(C.addressof(v), sig.ctypes.data, C.addressof(mp), rec.ctypes.data, out.ctypes.data)
     L.orc_pose_set_frame_diag(None, 0, None)
-    if diag:
-        return rec[0], out[:nk], chi2[:4 * nk].reshape(4, nk), stop
-    return rec[0], out[:nk]
+    return (rec[0], out[:nk]) + ((chi2[:4 * nk].reshape(4, nk), stop) if diag else ()) + (
+        (_trials_off(L, tb),) if trials else ())
 
 
 def _mappoints(match_lf, lf_points, match_mp, mps):

@@ -36,6 +36,13 @@ using namespace g2o_oracle;
 // end the optimisation, :163).  Null = off.
 thread_local float* g_diag_chi2 = nullptr;
 thread_local double* g_diag_stop = nullptr;
+// Per-trial record for tests/test_pose_edges_cpu.py (orc_pose_set_trials): 5 doubles per trial of
+// the Levenberg loop, in the order they ran: round, iteration, accepted (1 / 0), ok2 (the damped
+// solve succeeded), |currentChi - tempChi| / currentChi (infinity when the solve failed or
+// currentChi is 0).  g_trials_n counts every trial since the buffer was set, recorded or not.
+thread_local double* g_trials = nullptr;
+thread_local int g_trials_cap = 0;
+thread_local int g_trials_n = 0;
 
 struct UEdge {
     double Xw[3];
@@ -111,6 +118,7 @@ struct PoseOpt {
     double lambda = 0, ni = 2;
     int nBad = 0;
     int iters = 0;
+    int round = 0;  // of the 4 optimisations (the trial record's first column)
     double* stop_margin = nullptr;
 
     explicit PoseOpt(std::vector<UEdge>& e) : E(e) {}
@@ -185,6 +193,7 @@ struct PoseOpt {
         do {
             const SE3 T0 = T;
             const bool ok2 = solve(lambda);
+            const double chi0 = currentChi;  // the trial is judged against it (the record below)
             if (ok2) T = se3_mul(se3_exp(x), T);
             else for (double& v : x) v = 0;
             compute_active_errors();
@@ -205,6 +214,18 @@ struct PoseOpt {
                 T = T0;
             }
             qmax++;
+            if (g_trials) {
+                if (g_trials_n < g_trials_cap) {
+                    double* t = g_trials + 5 * g_trials_n;
+                    t[0] = round;
+                    t[1] = iteration;
+                    t[2] = rho > 0 && std::isfinite(tempChi) ? 1 : 0;
+                    t[3] = ok2 ? 1 : 0;
+                    t[4] = ok2 && chi0 > 0 ?std::fabs(chi0 - tempChi) / chi0
+                                                 : std::numeric_limits<double>::infinity();
+                }
+                g_trials_n++;
+            }
             if (trace_trials()) std::fputc(rho > 0 && std::isfinite(tempChi) ? 'A' : 'R', stderr);
         } while (rho < 0 && qmax < 10);
         if (trace_trials()) std::fputc('|', stderr);
@@ -261,6 +282,7 @@ extern "C" int orc_pose_optimization(orbmi_pose_frame* f, const orbmi_pose_obs* 
     for (int it = 0; it < 4; it++) {
         P.T = se3_from_tcw(f->tcw);
         P.stop_margin = g_diag_stop ? &g_diag_stop[it] : nullptr;
+        P.round = it;
         P.optimize(10);
         nBad = 0;
         // mono edges first, then stereo (the reference's two loops; order is immaterial here)
@@ -294,3 +316,12 @@ extern "C" void orc_pose_set_diag(float* chi2_rounds, double* stop_margin) {
     g_diag_chi2 = chi2_rounds;
     g_diag_stop = stop_margin;
 }
+
+// Trial record on (cap records of 5 doubles, filled from the start by the frames that follow) or
+// off (null); orc_pose_trial_count = trials run since the last orc_pose_set_trials.
+extern "C" void orc_pose_set_trials(double* buf, int cap) {
+    g_trials = buf;
+    g_trials_cap = buf ? cap : 0;
+    g_trials_n = 0;
+}
+extern "C" int orc_pose_trial_count() { return g_trials_n; }
