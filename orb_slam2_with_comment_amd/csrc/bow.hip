@@ -356,15 +356,7 @@ struct orbmi_vocabulary {
 
 namespace {
 
-bool on_device(const void* p) {
-    if (!p) return false;
-    hipPointerAttribute_t a;
-    if (hipPointerGetAttributes(&a, p) != hipSuccess) {
-        (void)hipGetLastError();
-        return false;
-    }
-    return a.type == hipMemoryTypeDevice;
-}
+using orbmi::on_device;  // orbmi_common.h
 
 size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 

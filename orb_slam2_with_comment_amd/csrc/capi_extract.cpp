@@ -218,15 +218,7 @@ int orbmi_compute_stereo_matches_batch_device(orbmi_extractor* h, float bf, floa
 
 namespace {
 
-bool rgbd_on_device(const void* p) {
-    if (!p) return false;
-    hipPointerAttribute_t at;
-    if (hipPointerGetAttributes(&at, p) != hipSuccess) {
-        (void)hipGetLastError();
-        return false;
-    }
-    return at.type == hipMemoryTypeDevice || at.type == hipMemoryTypeManaged;
-}
+using orbmi::on_device;  // orbmi_common.h
 
 // Device buffers of one operator call, freed when it returns (the operator forms synchronise).
 struct RgbdScratch {
@@ -270,7 +262,7 @@ int rgbd_operator(hipStream_t stream, const orbmi_keypoint* d_keys, int nk, cons
     if (nk <= 0) return ORBMI_OK;
     RgbdScratch scratch;
     const void* d_depth = depth;
-    if (!rgbd_on_device(depth)) {
+    if (!on_device(depth)) {
         // (the last row ends with its pixels: a view into a larger array owns no pitch padding there)
         const size_t bytes = (size_t)(rows - 1) * depth_step + (size_t)cols * (depth_type == ORBMI_DEPTH_U16 ? 2 : 4);
         void* d = scratch.take(bytes);
@@ -278,7 +270,7 @@ int rgbd_operator(hipStream_t stream, const orbmi_keypoint* d_keys, int nk, cons
         ORBMI_HIP(hipMemcpyAsync(d, depth, bytes, hipMemcpyHostToDevice, stream));
         d_depth = d;
     }
-    const bool kd = rgbd_on_device(keys_un), ud = rgbd_on_device(u_right), dd = rgbd_on_device(depth_out);
+    const bool kd = on_device(keys_un), ud = on_device(u_right), dd = on_device(depth_out);
     orbmi_keypoint* d_un = kd ? keys_un : (orbmi_keypoint*)scratch.take((size_t)nk * sizeof(orbmi_keypoint));
     float* d_ur = ud ? u_right : (float*)scratch.take((size_t)nk * sizeof(float));
     float* d_dep = dd ? depth_out : (float*)scratch.take((size_t)nk * sizeof(float));
@@ -342,7 +334,7 @@ int orbmi_compute_stereo_from_rgbd_keys(int device, const orbmi_keypoint* keys, 
     ORBMI_HIP(hipStreamCreateWithFlags(&st.s, hipStreamNonBlocking));
     RgbdScratch scratch;
     const orbmi_keypoint* d_keys = keys;
-    if (!rgbd_on_device(keys)) {
+    if (!on_device(keys)) {
         void* d = scratch.take((size_t)n * sizeof(orbmi_keypoint));
         if (!d) return ORBMI_E_HIP;
         ORBMI_HIP(hipMemcpyAsync(d, keys, (size_t)n * sizeof(orbmi_keypoint), hipMemcpyHostToDevice, st.s));
@@ -363,14 +355,14 @@ int orbmi_cvt_gray(int device, const uint8_t* image, size_t image_step, int chan
     RgbdScratch scratch;
     const uint8_t* d_src = image;
     size_t src_step = image_step;
-    if (!rgbd_on_device(image)) {
+    if (!on_device(image)) {
         src_step = (size_t)cols * channels;
         uint8_t* d = (uint8_t*)scratch.take((size_t)rows * src_step);
         if (!d) return ORBMI_E_HIP;
         ORBMI_HIP(hipMemcpy2DAsync(d, src_step, image, image_step, src_step, rows, hipMemcpyHostToDevice, st.s));
         d_src = d;
     }
-    const bool gd = rgbd_on_device(gray);
+    const bool gd = on_device(gray);
     uint8_t* d_dst = gd ? gray : (uint8_t*)scratch.take((size_t)rows * cols);
     if (!d_dst) return ORBMI_E_HIP;
     const int rc = orbmi::cvt_gray_run(st.s, d_src, src_step, channels, rgb ? 1 : 0, rows, cols, d_dst,

@@ -2,7 +2,7 @@
 // VertexSim3Expmap / EdgeSim3 linearised numerically one evaluation per lane, assembled by a gather
 // in edge order, solved by a block-sparse LDL^T in one workgroup, and the two arithmetic loops of
 // LoopClosing::CorrectLoop.  The arithmetic is csrc/essgraph.h, shared with the host; the Levenberg
-// decisions are taken on the host (capi_match.cpp) from one small read-back per trial.
+// decisions are taken on the host (capi_loop.cpp) from one small read-back per trial.
 #include "orbmi_common.h"
 #include "essgraph_launch.h"
 #include "wave_ops.h"

@@ -1,4 +1,4 @@
-// Launch interface of the essential-graph kernels (essgraph.hip), used by capi_match.cpp.
+// Launch interface of the essential-graph kernels (essgraph.hip), used by capi_loop.cpp.
 #pragma once
 #include "matcher.h"
 #include "essgraph.h"

@@ -177,15 +177,7 @@ struct orbmi_kfdb {
 
 namespace {
 
-bool kfdb_on_device(const void* p) {
-    if (!p) return false;
-    hipPointerAttribute_t at;
-    if (hipPointerGetAttributes(&at, p) != hipSuccess) {
-        (void)hipGetLastError();
-        return false;
-    }
-    return at.type == hipMemoryTypeDevice || at.type == hipMemoryTypeManaged;
-}
+using orbmi::on_device;  // orbmi_common.h
 
 // layout of the query upload: [max_common 16 B][q_value nq f64][q_word nq u32][list n i32]
 struct InLayout { size_t value, word, list, total; };
@@ -220,8 +212,8 @@ int stage_query(orbmi_kfdb* db, const uint32_t* q_word, const double* q_value, i
                 InLayout* Lout) {
     const InLayout L = in_layout(nq, (int)list.size());
     *Lout = L;
-    const bool dev = nq > 0 && kfdb_on_device(q_word);
-    if (nq > 0 && dev != kfdb_on_device(q_value)) return ORBMI_E_ARG;
+    const bool dev = nq > 0 && on_device(q_word);
+    if (nq > 0 && dev != on_device(q_value)) return ORBMI_E_ARG;
     memset(db->h_in, 0, 16);
     if (!list.empty()) memcpy(db->h_in + L.list, list.data(), list.size() * sizeof(int));
     if (nq > 0 && !dev) {
@@ -384,8 +376,8 @@ int orbmi_kfdb_store(orbmi_kfdb* db, int32_t kf_id, const uint32_t* word, const 
     std::lock_guard<std::mutex> lock(db->mu);
     ORBMI_HIP(hipSetDevice(db->device));
     if (slot_of(db, kf_id) >= 0) return ORBMI_E_STATE;
-    const bool dev = n > 0 && kfdb_on_device(word);
-    if (n > 0 && dev != kfdb_on_device(value)) return ORBMI_E_ARG;
+    const bool dev = n > 0 && on_device(word);
+    if (n > 0 && dev != on_device(value)) return ORBMI_E_ARG;
     if (!dev)
         for (int i = 1; i < n; i++)
             if (word[i] <= word[i - 1]) return ORBMI_E_ARG;

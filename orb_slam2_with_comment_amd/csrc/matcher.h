@@ -1,4 +1,4 @@
-// Host-side state of the device matchers (matcher.hip, capi_match.cpp).
+// Host-side state of the device matchers (matcher.hip; the C entries in capi_match.cpp, capi_mapping.cpp, capi_loop.cpp).
 #pragma once
 #include <vector>
 

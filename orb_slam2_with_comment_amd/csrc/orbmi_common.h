@@ -49,7 +49,19 @@ __device__ inline int popc256(const uint4& a0, const uint4& a1, const uint4& b0,
            __popc(a1.x ^ b1.x) + __popc(a1.y ^ b1.y) + __popc(a1.z ^ b1.z) + __popc(a1.w ^ b1.w);
 }
 
-// Non-blocking stream of one handle.  ORBMI_PRIO_<ROLE>=high|low (ROLE = MATCHER, POSE, BA,
+// Whether a kernel can read p in place: device or managed memory (host only; a null pointer and
+// pageable or pinned host memory are not)
+inline bool on_device(const void* p) {
+    if (!p) return false;
+    hipPointerAttribute_t at;
+    if (hipPointerGetAttributes(&at, p) != hipSuccess) {
+        (void)hipGetLastError();
+        return false;
+    }
+    return at.type == hipMemoryTypeDevice || at.type == hipMemoryTypeManaged;
+}
+
+// Non-blocking stream of one handle. ORBMI_PRIO_<ROLE>=high|low (ROLE = MATCHER, POSE, BA,
 // VOCAB, EXTRACTOR) selects the device's greatest / least stream priority, else the default.
 inline hipError_t stream_create(hipStream_t* s, const char* role) {
     char key[64];

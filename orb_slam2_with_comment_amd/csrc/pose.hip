@@ -815,15 +815,7 @@ hipStream_t orbmi_extractor_stream_(orbmi_extractor* ex);  // capi_extract.cpp
 
 namespace {
 
-bool is_device_ptr(const void* p) {
-    if (!p) return false;
-    hipPointerAttribute_t a;
-    if (hipPointerGetAttributes(&a, p) != hipSuccess) {
-        (void)hipGetLastError();
-        return false;
-    }
-    return a.type == hipMemoryTypeDevice;
-}
+using orbmi::on_device;  // orbmi_common.h
 
 // event pair for the next profiled launch (grown on demand, reused after each read)
 std::pair<hipEvent_t, hipEvent_t>* next_events(orbmi_pose* h) {
@@ -927,9 +919,9 @@ int orbmi_pose_optimization(orbmi_pose* h, orbmi_pose_frame* frames, int nframes
     if (!h || nframes < 0 || nobs < 0 || (nframes && !frames) || (nobs && (!obs || !outlier))) return ORBMI_E_ARG;
     if (nframes == 0) return ORBMI_OK;
     ORBMI_HIP(hipSetDevice(h->device));
-    const bool dev = is_device_ptr(frames);
-    if (dev != is_device_ptr(obs) && nobs) return ORBMI_E_ARG;
-    if (nobs && dev != is_device_ptr(outlier)) return ORBMI_E_ARG;
+    const bool dev = on_device(frames);
+    if (dev != on_device(obs) && nobs) return ORBMI_E_ARG;
+    if (nobs && dev != on_device(outlier)) return ORBMI_E_ARG;
     if (dev) {
         hipLaunchKernelGGL((k_pose_opt<false, false>), dim3(nframes), dim3(kPoseThreads), 0, h->stream, frames, obs, outlier, 0,
                            nullptr, PoseGatherArgs{});
@@ -978,9 +970,9 @@ int pose_frame(orbmi_pose* h, const orbmi_frame_view* F, const float* inv_level_
     if (F->nlevels < 1 || F->nlevels > kMaxLevels || (F->n > 0 && !F->keys_un)) return ORBMI_E_ARG;
     if ((mp->match_lf && (!mp->lf_points || mp->n_lf_points < 0)) || (mp->match_mp && (!mp->mps || mp->n_mps < 0)))
         return ORBMI_E_ARG;
-    if (F->n_device && !is_device_ptr(F->n_device)) return ORBMI_E_ARG;
+    if (F->n_device && !on_device(F->n_device)) return ORBMI_E_ARG;
     ORBMI_HIP(hipSetDevice(h->device));
-    const bool async = is_device_ptr(rec) && is_device_ptr(outlier);
+    const bool async = on_device(rec) && on_device(outlier);
     const size_t n = (size_t)std::max(F->n, 1);
     if (n > h->cap_obs) {
         if (h->d_obs) { ORBMI_HIP(hipStreamSynchronize(h->stream)); (void)hipFree(h->d_obs); }
@@ -990,7 +982,7 @@ int pose_frame(orbmi_pose* h, const orbmi_frame_view* F, const float* inv_level_
         h->cap_obs = n;
     }
     // staging of host inputs / outputs: one block, sized for this call
-    auto host_bytes = [&](const void* p, size_t b) { return (p && !is_device_ptr(p)) ? ((b + 255) & ~(size_t)255) : 0; };
+    auto host_bytes = [&](const void* p, size_t b) { return (p && !on_device(p)) ? ((b + 255) & ~(size_t)255) : 0; };
     const size_t need = host_bytes(F->keys_un, n * sizeof(orbmi_keypoint)) + host_bytes(F->u_right, n * 4) +
                         host_bytes(mp->match_lf, n * 4) + host_bytes(mp->match_mp, n * 4) +
                         (mp->match_lf ? host_bytes(mp->lf_points, mp->n_lf_points * sizeof(orbmi_lastframe_point)) : 0) +
@@ -1007,14 +999,14 @@ int pose_frame(orbmi_pose* h, const orbmi_frame_view* F, const float* inv_level_
     }
     int rc = ORBMI_OK;
     auto dev_in = [&](const void* p, size_t b) -> const void* {
-        if (!p || is_device_ptr(p) || b == 0) return p;
+        if (!p || on_device(p) || b == 0) return p;
         uint8_t* d = h->d_stage + h->used_stage;
         h->used_stage += (b + 255) & ~(size_t)255;
         if (hipMemcpyAsync(d, p, b, hipMemcpyHostToDevice, h->stream) != hipSuccess) rc = ORBMI_E_HIP;
         return d;
     };
     auto dev_out = [&](void* p, size_t b) -> void* {
-        if (is_device_ptr(p)) return p;
+        if (on_device(p)) return p;
         uint8_t* d = h->d_stage + h->used_stage;
         h->used_stage += (b + 255) & ~(size_t)255;
         return d;
@@ -1024,7 +1016,7 @@ int pose_frame(orbmi_pose* h, const orbmi_frame_view* F, const float* inv_level_
     a.n_dev = F->n_device;
     a.keys = (const orbmi_keypoint*)dev_in(F->keys_un, n * sizeof(orbmi_keypoint));
     a.u_right = (const float*)dev_in(F->u_right, n * 4);
-    if (is_device_ptr(F->tcw)) a.tcw_dev = F->tcw;
+    if (on_device(F->tcw)) a.tcw_dev = F->tcw;
     else memcpy(a.tcw, F->tcw, sizeof(a.tcw));
     a.fx = F->fx; a.fy = F->fy; a.cx = F->cx; a.cy = F->cy; a.bf = F->bf;
     for (int l = 0; l < F->nlevels; l++) a.inv_sigma2[l] = inv_level_sigma2[l];
@@ -1055,9 +1047,9 @@ int pose_frame(orbmi_pose* h, const orbmi_frame_view* F, const float* inv_level_
     ORBMI_HIP(hipGetLastError());
     if (ev) ORBMI_HIP(hipEventRecord(ev->second, h->stream));
     if (async) return ORBMI_OK;
-    if (!is_device_ptr(rec))
+    if (!on_device(rec))
         ORBMI_HIP(hipMemcpyAsync(rec, a.rec, sizeof(orbmi_pose_frame), hipMemcpyDeviceToHost, h->stream));
-    if (!is_device_ptr(outlier))
+    if (!on_device(outlier))
         ORBMI_HIP(hipMemcpyAsync(outlier, a.outlier, (size_t)std::max(F->n, 0), hipMemcpyDeviceToHost, h->stream));
     ORBMI_HIP(hipStreamSynchronize(h->stream));
     h->used_stage = 0;
@@ -1079,8 +1071,8 @@ int orbmi_pose_optimization_frame_track(orbmi_pose* h, const orbmi_frame_view* F
                                         int stage, uint8_t* occupied_out, int* counts) {
     if (!h || !mp || !counts || (stage != 0 && stage != 1)) return ORBMI_E_ARG;
     // one asynchronous launch: every array it reads or writes lives on the device
-    auto dev = [](const void* p) { return !p || is_device_ptr(p); };
-    if (!is_device_ptr(rec) || !is_device_ptr(outlier) || !is_device_ptr(counts) || !dev(occupied_out) ||
+    auto dev = [](const void* p) { return !p || on_device(p); };
+    if (!on_device(rec) || !on_device(outlier) || !on_device(counts) || !dev(occupied_out) ||
         !dev(mp->match_lf) || !dev(mp->match_mp) || (mp->match_lf && !dev(mp->lf_points)) ||
         (mp->match_mp && !dev(mp->mps)))
         return ORBMI_E_ARG;

@@ -1,4 +1,4 @@
-// Launch interface of the batched Sim3Solver kernel (sim3.hip), used by capi_match.cpp.
+// Launch interface of the batched Sim3Solver kernel (sim3.hip), used by capi_loop.cpp.
 #pragma once
 #include "matcher.h"
 
