@@ -533,6 +533,50 @@ int orbmi_ba_set_enqueued_hook(orbmi_ba* b, void (*fn)(void*), void* arg);
 int orbmi_local_bundle_adjustment(orbmi_ba* h, const orbmi_ba_problem* problem, orbmi_ba_result* result,
                                   const volatile int* stop);
 
+/* ---- Optimizer::BundleAdjustment (global BA) ------------------------------------------ */
+
+#define ORBMI_GBA_MAX_FREE_POSES 2048 /* optimised keyframes of one call; more: ORBMI_E_UNSUPPORTED */
+#define ORBMI_GBA_MAX_ITERATIONS 64   /* `iterations` of one call (the length of `trials`)          */
+#define ORBMI_GBA_TERMINATE 1    /* Levenberg stopped by a rule of its own (else: count or stop flag) */
+#define ORBMI_GBA_SOLVE_FAILED 2 /* a damped solve met a pivot that is not a positive finite number  */
+#define ORBMI_GBA_REJECTED 4     /* a trial was rejected and the estimates restored                  */
+
+typedef struct orbmi_gba_result {
+    float* tcw;                    /* nkf x 16; fixed keyframes and keyframes that no edge names
+                                    * come back as given, bit for bit                            */
+    float* pos;                    /* npt x 3; a point without an edge comes back as given      */
+    uint8_t* included;             /* npt: !vbNotIncludedMP (the point has at least one edge)    */
+    int iterations;                /* iterations of optimize() run                               */
+    int trials[ORBMI_GBA_MAX_ITERATIONS]; /* Levenberg trials (qmax) of iteration k; 0 beyond     */
+    double chi2_initial;           /* activeRobustChi2 at the first linearisation                */
+    double chi2;                   /* activeRobustChi2 of the errors as the last trial left them */
+    int stop_check;                /* index of the first stop-flag check that found it raised, -1: none */
+    int checks;                    /* stop-flag checks made by the call                          */
+    int status;                    /* ORBMI_GBA_* or'ed                                          */
+    int n_free;                    /* pose blocks of the reduced camera system                   */
+    int n_blocks;                  /* non-zero 6 x 6 blocks (i >= j) of S before elimination     */
+    double phase_ms[4];            /* with ORBMI_GBA_PROFILE set in the environment: device time of
+                                    * linearise, Schur, factor + solve, update + chi2; else 0   */
+} orbmi_gba_result;
+
+/* Optimizer::BundleAdjustment(vpKFs, vpMP, nIterations, pbStopFlag, nLoopKF, bRobust)
+ * (src/Optimizer.cc:56-255) on the assembled graph: one optimize(iterations) of g2o's Levenberg over
+ * BlockSolver_6_3, Huber sqrt(5.99) / sqrt(7.815) when `robust`, no outlier levels.  It runs on an
+ * orbmi_ba handle and honours orbmi_ba_set_stream and orbmi_ba_set_stop_at_check.  `fixed` is taken
+ * as given; orbmi_ba_point.bad is ignored (the caller leaves bad vertices out).  Edges grouped by
+ * point with at most one per (point, keyframe), as orbmi_local_bundle_adjustment; else ORBMI_E_ARG.
+ * The stop-flag checks, numbered from 0 in the order g2o reads them: optimize's loop condition
+ * before each iteration while i < iterations, and the Levenberg inner loop's condition after a
+ * rejected trial while qmax < 10.  There is none before or after the optimisation; whatever
+ * estimate stands when the flag is seen is written back (skipping the map update is the caller's
+ * rule).  The reduced camera system is dense and sized from the problem: any number of keyframes,
+ * up to ORBMI_GBA_MAX_FREE_POSES optimised ones, checked before anything is allocated or
+ * launched (ORBMI_E_UNSUPPORTED).  ORBMI_E_ARG: a NULL array, a negative count, iterations outside
+ * [0, ORBMI_GBA_MAX_ITERATIONS], an edge index out of range.  Every loop is bounded: any input
+ * terminates, with ORBMI_GBA_SOLVE_FAILED where a solve failed.  Synchronous; host arrays. */
+int orbmi_bundle_adjustment(orbmi_ba* h, const orbmi_ba_problem* problem, int iterations, int robust,
+                            orbmi_gba_result* result, const volatile int* stop);
+
 /* ---- Optimizer::PoseOptimization ---------------------------------------------------- */
 
 /* One unary edge: a keypoint i of the Frame with a MapPoint (mvpMapPoints[i] != NULL),

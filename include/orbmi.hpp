@@ -446,8 +446,22 @@ public:
     // the deterministic pbStopFlag of orbmi_ba_set_stop_at_check (k < 0: off)
     void SetStopAtCheck(int k) { check(orbmi_ba_set_stop_at_check(h_, k), "orbmi_ba_set_stop_at_check"); }
 
+    orbmi_ba* handle() const { return h_; }
+
 private:
     orbmi_ba* h_ = nullptr;
+};
+
+// The graph of Optimizer::BundleAdjustment (src/Optimizer.cc:78-200) over plain vectors, as
+// orbmi_bundle_adjustment takes it, and what comes back (orbmi_gba_result).
+struct BundleAdjustmentOutput {
+    std::vector<float> Tcw;             // nkf x 16
+    std::vector<float> pos;             // npt x 3
+    std::vector<uint8_t> included;      // npt: !vbNotIncludedMP
+    int iterations = 0, status = 0;     // status: ORBMI_GBA_* or'ed
+    std::vector<int> trials;            // per iteration
+    double chi2Initial = 0, chi2 = 0;
+    int stop_check = -1, checks = 0;
 };
 
 // ORB_SLAM2::Sim3Solver (include/Sim3Solver.h:37-130, src/Sim3Solver.cc) over the flat arrays the
@@ -691,6 +705,42 @@ struct Optimizer {
         out.status = r.status;
         out.trials.assign(r.trials, r.trials + r.iterations);
         return out;
+    }
+
+    // void Optimizer::BundleAdjustment(vpKFs, vpMP, nIterations, pbStopFlag, nLoopKF, bRobust) on the
+    // assembled graph (src/Optimizer.cc:56-255, from the vertices and edges on); the write-back by
+    // nLoopKF stays the caller's.  It runs on a LocalBundleAdjuster's handle.
+    static BundleAdjustmentOutput BundleAdjustment(LocalBundleAdjuster& ba, const std::vector<orbmi_ba_keyframe>& kfs,
+                                                   const std::vector<orbmi_ba_point>& pts, const std::vector<orbmi_ba_edge>& edges,
+                                                   int nIterations = 5, const volatile int* pbStopFlag = nullptr,
+                                                   bool bRobust = true) {
+        BundleAdjustmentOutput out;
+        out.Tcw.assign(kfs.size() * 16, 0.0f);
+        out.pos.assign(pts.size() * 3, 0.0f);
+        out.included.assign(pts.size(), 0);
+        orbmi_ba_problem p{(int)kfs.size(), (int)pts.size(), (int)edges.size(), kfs.data(), pts.data(), edges.data()};
+        orbmi_gba_result r{};
+        r.tcw = out.Tcw.data();
+        r.pos = out.pos.data();
+        r.included = out.included.data();
+        check(orbmi_bundle_adjustment(ba.handle(), &p, nIterations, bRobust ? 1 : 0, &r, pbStopFlag), "orbmi_bundle_adjustment");
+        out.iterations = r.iterations;
+        out.status = r.status;
+        out.trials.assign(r.trials, r.trials + nIterations);
+        out.chi2Initial = r.chi2_initial;
+        out.chi2 = r.chi2;
+        out.stop_check = r.stop_check;
+        out.checks = r.checks;
+        return out;
+    }
+
+    // void Optimizer::GlobalBundleAdjustemnt(pMap, nIterations, pbStopFlag, nLoopKF, bRobust)
+    // (src/Optimizer.cc:47-53), the reference's spelling: BundleAdjustment over the whole map
+    static BundleAdjustmentOutput GlobalBundleAdjustemnt(LocalBundleAdjuster& ba, const std::vector<orbmi_ba_keyframe>& kfs,
+                                                         const std::vector<orbmi_ba_point>& pts,
+                                                         const std::vector<orbmi_ba_edge>& edges, int nIterations = 5,
+                                                         const volatile int* pbStopFlag = nullptr, bool bRobust = true) {
+        return BundleAdjustment(ba, kfs, pts, edges, nIterations, pbStopFlag, bRobust);
     }
 
     // The map-point loop of CorrectLoop / OptimizeEssentialGraph (src/LoopClosing.cc:607-612,

@@ -78,6 +78,7 @@ _PROTOS = {
     "orbmi_ba_create": (_i, [_i, C.POINTER(_vp)]),
     "orbmi_ba_destroy": (None, [_vp]),
     "orbmi_local_bundle_adjustment": (_i, [_vp, _vp, _vp, _vp]),
+    "orbmi_bundle_adjustment": (_i, [_vp, _vp, _i, _i, _vp, _vp]),
     "orbmi_pose_create": (_i, [_i, C.POINTER(_vp)]),
     "orbmi_pose_destroy": (None, [_vp]),
     "orbmi_pose_optimization": (_i, [_vp, _vp, _i, _vp, _i, _vp]),

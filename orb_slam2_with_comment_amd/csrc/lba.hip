@@ -58,6 +58,9 @@
 // bit-exact extractor / matcher sources keep -ffp-contract=off)
 #pragma clang fp contract(fast)
 
+#include "ba_edge.h"    // the edge arithmetic, under the contraction mode set above
+#include "ba_handle.h"  // struct orbmi_ba
+
 namespace orbmi {
 
 constexpr int kBaMaxPoses = 30;                        // 6*30 = 180 unknowns
@@ -163,103 +166,7 @@ __device__ inline void ba_use(BaDev& a, int L) {
 }
 
 // ---------------------------------------------------------------- edges
-__device__ inline bool edge_stereo(const orbmi_ba_edge& e) { return !(e.ur < 0); }
-
-// The edge math works on values (the edge record, its keyframe's camera, the pose Tk) so that a
-// kernel can load them once, early, and keep them in registers; the a-based helpers below load
-// them from the arrays.
-struct BaCam { float fx, fy, cx, cy, bf; };
-__device__ inline BaCam ba_cam(const orbmi_ba_keyframe& k) { return BaCam{k.fx, k.fy, k.cx, k.cy, k.bf}; }
-
-// error of edge e with the point's position at Xp (3 doubles)
-__device__ inline void edge_err_math(const orbmi_ba_edge& e, const BaCam& kf, const double* Tk, const double* Xp,
-                                     double* err) {
-    double p[3];
-    se3_map(Tk, Xp, p);
-    if (!edge_stereo(e)) {
-        const double px = p[0] / p[2], py = p[1] / p[2];
-        err[0] = (double)e.u - (px * (double)kf.fx + (double)kf.cx);
-        err[1] = (double)e.v - (py * (double)kf.fy + (double)kf.cy);
-        err[2] = 0;
-    } else {
-        const float invz = (float)(1.0f / p[2]);  // float invz (types_six_dof_expmap.cpp:151)
-        const double r0 = p[0] * invz * (double)kf.fx + (double)kf.cx;
-        const double r1 = p[1] * invz * (double)kf.fy + (double)kf.cy;
-        const double r2 = r0 - (double)(kf.bf * invz);
-        err[0] = (double)e.u - r0;
-        err[1] = (double)e.v - r1;
-        err[2] = (double)e.ur - r2;
-    }
-}
-
-__device__ inline double edge_chi2_math(const orbmi_ba_edge& e, const double* r) {
-    const double info = (double)e.inv_sigma2;
-    return r[0] * (info * r[0]) + r[1] * (info * r[1]) + (edge_stereo(e) ? r[2] * (info * r[2]) : 0.0);
-}
-
-__device__ inline double huber_delta(const orbmi_ba_edge& e) {
-    // const float thHuberMono = sqrt(5.991), thHuberStereo = sqrt(7.815) (src/Optimizer.cc:599-600)
-    const float th = edge_stereo(e) ? (float)sqrt(7.815) : (float)sqrt(5.991);
-    return (double)th;
-}
-
-// robustified chi2 and weight rho' (RobustKernelHuber::robustify); fl = the edge's eflag
-__device__ inline void edge_robust_math(unsigned char fl, const orbmi_ba_edge& e, double c, double* rho0, double* rho1) {
-    if (fl & 2) { *rho0 = c; *rho1 = 1.0; return; }
-    const double d = huber_delta(e), dsqr = d * d;
-    if (c <= dsqr) { *rho0 = c; *rho1 = 1.0; }
-    else { const double s = sqrt(c); *rho0 = 2 * s * d - dsqr; *rho1 = d / s; }
-}
-
-// Jacobians (types_six_dof_expmap.cpp:103-134, :188-234)
-__device__ inline void edge_jac_math(const orbmi_ba_edge& e, const BaCam& kf, const double* Tk, const double* Xp,
-                                     double Jl[3][3], double Jp[3][6]) {
-    double p[3], R[3][3];
-    se3_map(Tk, Xp, p);
-    q_to_matrix(load_q(Tk), R);
-    // one reciprocal per edge (fast_rcp: within an ulp of 1 / z) instead of the reference's
-    // divisions; the Jacobians only steer the Levenberg steps (parity 1e-4), the errors and
-    // chi2 keep the exact divisions
-    const double x = p[0], y = p[1], z = p[2], iz = fast_rcp(z), iz2 = iz * iz;
-    const double fx = kf.fx, fy = kf.fy, bf = kf.bf;
-    if (!edge_stereo(e)) {
-        const double t02 = -x * iz * fx, t12 = -y * iz * fy;
-        for (int c = 0; c < 3; c++) {
-            Jl[0][c] = -iz * (fx * R[0][c] + t02 * R[2][c]);
-            Jl[1][c] = -iz * (fy * R[1][c] + t12 * R[2][c]);
-            Jl[2][c] = 0;
-        }
-    } else {
-        for (int c = 0; c < 3; c++) {
-            Jl[0][c] = -fx * R[0][c] * iz + fx * x * R[2][c] * iz2;
-            Jl[1][c] = -fy * R[1][c] * iz + fy * y * R[2][c] * iz2;
-            Jl[2][c] = Jl[0][c] - bf * R[2][c] * iz2;
-        }
-    }
-    Jp[0][0] = x * y * iz2 * fx; Jp[0][1] = -(1 + (x * x * iz2)) * fx; Jp[0][2] = y * iz * fx;
-    Jp[0][3] = -iz * fx; Jp[0][4] = 0; Jp[0][5] = x * iz2 * fx;
-    Jp[1][0] = (1 + y * y * iz2) * fy; Jp[1][1] = -x * y * iz2 * fy; Jp[1][2] = -x * iz * fy;
-    Jp[1][3] = 0; Jp[1][4] = -iz * fy; Jp[1][5] = y * iz2 * fy;
-    if (edge_stereo(e)) {
-        Jp[2][0] = Jp[0][0] - bf * y * iz2; Jp[2][1] = Jp[0][1] + bf * x * iz2; Jp[2][2] = Jp[0][2];
-        Jp[2][3] = Jp[0][3]; Jp[2][4] = 0; Jp[2][5] = Jp[0][5] - bf * iz2;
-    } else {
-        for (int c = 0; c < 6; c++) Jp[2][c] = 0;
-    }
-}
-
-// weight W = rho' * info and omega_r = -info * e * rho' (constructQuadraticForm), err = the
-// edge's current error
-__device__ inline void edge_weights_math(unsigned char fl, const orbmi_ba_edge& ed, const double* err, double* w,
-                                         double om[3]) {
-    const double info = (double)ed.inv_sigma2;
-    double r0, r1;
-    edge_robust_math(fl, ed, edge_chi2_math(ed, err), &r0, &r1);
-    *w = (fl & 2) ? info : r1 * info;
-    const double s = (fl & 2) ? 1.0 : r1;
-    for (int k = 0; k < 3; k++) om[k] = -(info * err[k]) * s;
-}
-
+// (the edge arithmetic itself is ba_edge.h, shared with gba.hip)
 // the a-based forms (they load the edge, its keyframe and pose from the arrays)
 __device__ inline void edge_error_at(const BaDev& a, int i, const double* T, const double* Xp, double* err) {
     const orbmi_ba_edge e = a.edges[i];
@@ -273,7 +180,7 @@ __device__ inline void edge_error(const BaDev& a, int i, const double* T, const 
 __device__ inline double edge_chi2(const BaDev& a, int i) { return edge_chi2_math(a.edges[i], a.err + 3 * i); }
 
 __device__ inline void edge_robust(const BaDev& a, int i, double c, double* rho0, double* rho1) {
-    edge_robust_math(a.eflag[i], a.edges[i], c, rho0, rho1);
+    edge_robust_math(a.eflag[i], a.edges[i], ba_huber_local(), c, rho0, rho1);
 }
 
 // ---------------------------------------------------------------- block helpers
@@ -603,25 +510,6 @@ __global__ __launch_bounds__(kBaBlock) void k_ba_errors(BaDev a, int phase) {
 }
 
 // ---------------------------------------------------------------- linear system
-// D^-1 of the point's damped 3x3 block, Hll + lambda I (cofactors)
-__device__ inline void point_dinv(const double* Hll, int p, double lam, double Di[9]) {
-    double D[3][3];
-    for (int r = 0; r < 3; r++)
-        for (int c = 0; c < 3; c++) D[r][c] = Hll[9 * p + 3 * r + c] + (r == c ? lam : 0.0);
-    const double c00 = D[1][1] * D[2][2] - D[1][2] * D[2][1];
-    const double c10 = D[1][2] * D[2][0] - D[1][0] * D[2][2];
-    const double c20 = D[1][0] * D[2][1] - D[1][1] * D[2][0];
-    const double det = D[0][0] * c00 + D[0][1] * c10 + D[0][2] * c20;
-    const double id = 1.0 / det;
-    Di[0] = c00 * id; Di[3] = c10 * id; Di[6] = c20 * id;
-    Di[1] = (D[0][2] * D[2][1] - D[0][1] * D[2][2]) * id;
-    Di[4] = (D[0][0] * D[2][2] - D[0][2] * D[2][0]) * id;
-    Di[7] = (D[0][1] * D[2][0] - D[0][0] * D[2][1]) * id;
-    Di[2] = (D[0][1] * D[1][2] - D[0][2] * D[1][1]) * id;
-    Di[5] = (D[0][2] * D[1][0] - D[0][0] * D[1][2]) * id;
-    Di[8] = (D[0][0] * D[1][1] - D[0][1] * D[1][0]) * id;
-}
-
 // thread per edge: computeActiveErrors + robust chi2 (block partials), then
 // BaseBinaryEdge::constructQuadraticForm (base_binary_edge.hpp:55-120): Hpl block, the
 // edge's Hll / b_l and Hpp / b_p contributions.  Inactive edges into free poses write zeros,
@@ -643,25 +531,8 @@ __device__ inline void edge_linearize_math(const BaSys& y, int i, int pi, int kp
         }
         return;
     }
-    double Jl[3][3], Jp[3][6], w, om[3];
-    edge_jac_math(ed, kf, Tk, Xp, Jl, Jp);
-    edge_weights_math(fl, ed, err, &w, om);
     double* He = He_out ? He_out : y.Hle + 9 * (long long)i;
-    int q = 0;
-    for (int r = 0; r < 3; r++)
-        for (int c = r; c < 3; c++, q++)
-            He[q] = Jl[0][r] * w * Jl[0][c] + Jl[1][r] * w * Jl[1][c] + Jl[2][r] * w * Jl[2][c];
-    for (int r = 0; r < 3; r++) He[6 + r] = Jl[0][r] * om[0] + Jl[1][r] * om[1] + Jl[2][r] * om[2];
-    if (free_pose) {
-        for (int r = 0; r < 6; r++)
-            for (int c = 0; c < 3; c++)
-                B[r * 3 + c] = Jp[0][r] * w * Jl[0][c] + Jp[1][r] * w * Jl[1][c] + Jp[2][r] * w * Jl[2][c];
-        q = 0;
-        for (int r = 0; r < 6; r++)
-            for (int c = r; c < 6; c++, q++)
-                Hp[q] = Jp[0][r] * w * Jp[0][c] + Jp[1][r] * w * Jp[1][c] + Jp[2][r] * w * Jp[2][c];
-        for (int r = 0; r < 6; r++) Hp[21 + r] = Jp[0][r] * om[0] + Jp[1][r] * om[1] + Jp[2][r] * om[2];
-    }
+    edge_blocks_math(ed, kf, Tk, fl, ba_huber_local(), err, Xp, free_pose, He, B, Hp);
 }
 
 __device__ inline void edge_linearize(const BaDev& a, const BaSys& y, int i, int pi, bool active, const double* T,
@@ -707,7 +578,7 @@ __device__ inline double edge_trial(const BaDev& a, const BaSys& t, int i, const
         double* eo = a.err + 3 * i;
         eo[0] = err[0]; eo[1] = err[1]; eo[2] = err[2];
         double r1;
-        edge_robust_math(s.fl, s.e, edge_chi2_math(s.e, err), &r0, &r1);
+        edge_robust_math(s.fl, s.e, ba_huber_local(), edge_chi2_math(s.e, err), &r0, &r1);
     }
     edge_linearize_math(t, i, s.pi, s.kpos, active, s.e, s.cam, s.T, s.fl, err, Xp, He_out);
     return r0;
@@ -2101,30 +1972,6 @@ __global__ __launch_bounds__(kBaBlock) void k_ba_finish(BaDev a, float* __restri
 }  // namespace orbmi
 
 // ---------------------------------------------------------------- host
-struct orbmi_ba {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    bool own_stream = true;  // false after orbmi_ba_set_stream(b, s != NULL)
-    hipEvent_t done = nullptr;
-    uint8_t* d_buf = nullptr;
-    size_t cap = 0;
-    uint8_t* h_stage = nullptr;  // pinned staging of the uploaded graph (one H2D copy)
-    size_t cap_stage = 0;
-    hipEvent_t up_done = nullptr;  // the last upload from h_stage has been read
-    // the graph upload's own stream (created at the first call): the copy depends on nothing
-    // enqueued ahead of LocalBA on `stream` (a LocalMapping chain's searches), so it runs beside
-    // that work and `stream` waits for up_done only
-    hipStream_t up_stream = nullptr;
-    uint8_t* h_out = nullptr;      // pinned staging of the results (poses, positions, erase flags)
-    size_t cap_out = 0;
-    orbmi::BaCtl* h_ctl = nullptr;  // pinned readback of the LM control block
-    int* h_stop = nullptr;          // host-mapped mirror of the caller's stop flag
-    int* d_stop = nullptr;          //   (its device address)
-    int stop_at = -1;               // orbmi_ba_set_stop_at_check
-    void (*enqueued)(void*) = nullptr;  // orbmi_ba_set_enqueued_hook
-    void* enqueued_arg = nullptr;
-};
-
 namespace {
 
 using namespace orbmi;
@@ -2319,6 +2166,7 @@ void orbmi_ba_destroy(orbmi_ba* b) {
     }
     if (b->up_done) (void)hipEventDestroy(b->up_done);
     if (b->h_out) (void)hipHostFree(b->h_out);
+    if (b->h_gba) (void)hipHostFree(b->h_gba);
     if (b->stream && b->own_stream) (void)hipStreamDestroy(b->stream);
     delete b;
 }

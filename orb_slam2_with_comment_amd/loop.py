@@ -21,8 +21,13 @@ current_matched_points    mvpCurrentMatchedPoints as objects, from compute_sim3'
 correct_loop              LoopClosing::CorrectLoop on system.KeyFrame / system.MapPoint, from the
                           accepted Scw to the corrected poses and points.
 
+global_bundle_adjustment      Optimizer::GlobalBundleAdjustemnt: the whole map's graph, the device
+                              bundle adjustment and the write-back of src/Optimizer.cc:206-253.
+run_global_bundle_adjustment  LoopClosing::RunGlobalBundleAdjustment: that, then the spanning-tree
+                              propagation and the map points' carry-over.
+
 For detection the covisibility graph stays the caller's: it comes in as callables (or mappings)
-from a keyframe id to ids.  Global BA, monocular mode, DetectRelocalizationCandidates and the
+from a keyframe id to ids.  Monocular mode, DetectRelocalizationCandidates, the GBA thread and the
 call from the SLAM loops are not here.
 """
 from __future__ import annotations
@@ -179,6 +184,9 @@ class LoopBackend(DeviceBackend):
         if self._own_db and self.db is not None:
             self.db.close()
         self.db = None
+        if getattr(self, "_gba", None) is not None:
+            self._gba.close()
+            self._gba = None
         super().close()
 
     def search_by_bow_kf(self, cur, cand):
@@ -207,6 +215,13 @@ class LoopBackend(DeviceBackend):
 
     def correct_points_sim3(self, points, ref_index, Srw, Swr_corrected, poses):
         return self._essgraph().correct_points_sim3(points, ref_index, Srw, Swr_corrected, poses)
+
+    def bundle_adjustment(self, problem, iterations=10, robust=False, stop=None, stop_at_check=None):
+        """Optimizer::BundleAdjustment on the assembled graph (optimizer.GlobalBA.run)."""
+        if getattr(self, "_gba", None) is None:
+            from .optimizer import GlobalBA
+            self._gba = GlobalBA()
+        return self._gba.run(problem, iterations, robust, stop, -1 if stop_at_check is None else stop_at_check)
 
 
 class LoopDetector:
@@ -761,3 +776,90 @@ def correct_loop(cur, matched_kf, Scw, current_matched, loop_points, keyframes, 
     cur.loop_edges.append(matched_kf)
     return {"corrected_points": {i: len(per_kf[i]) for i in order}, "loop_fusion": fusion, "search_and_fuse": saf,
             "loop_connections": lc, "graph": G, "essential_graph": r}
+
+
+def global_bundle_adjustment(keyframes, map_points, loop_kf_id, backend, iterations=10, robust=False, stop=None,
+                             stop_at_check=None):
+    """Optimizer::GlobalBundleAdjustemnt (src/Optimizer.cc:47-53) = BundleAdjustment (:56-255) over
+    the map: optimizer.gather_global_ba, backend.bundle_adjustment, then the write-back of :206-253.
+    loop_kf_id == 0: straight into the poses and positions, with UpdateNormalAndDepth; otherwise
+    into tcw_gba / pos_gba with ba_global_for_kf = loop_kf_id.  The estimate is written back even
+    when the stop flag was seen, as the reference does.  -> the backend's result with "keyframes"
+    and "map_points" (the vertices, in array order) added."""
+    from .optimizer import gather_global_ba
+    from .system import update_normals_and_depths
+    problem, kfs, mps = gather_global_ba(keyframes, map_points)
+    r = dict(backend.bundle_adjustment(problem, iterations, robust, stop, stop_at_check))
+    for i, kf in enumerate(kfs):
+        T = np.asarray(r["tcw"][i], np.float32).reshape(4, 4).copy()
+        if loop_kf_id == 0:
+            kf.tcw = T
+        else:
+            kf.tcw_gba, kf.ba_global_for_kf = T, loop_kf_id
+    moved = []
+    for j, mp in enumerate(mps):
+        if not r["included"][j]:
+            continue
+        X = np.asarray(r["pos"][j], np.float32).copy()
+        if loop_kf_id == 0:
+            mp.pos = X
+            moved.append(mp)
+        else:
+            mp.pos_gba, mp.ba_global_for_kf = X, loop_kf_id
+    if moved:
+        update_normals_and_depths(moved)
+    r["keyframes"], r["map_points"] = kfs, mps
+    return r
+
+
+def run_global_bundle_adjustment(keyframes, map_points, origins, loop_kf_id, backend, iterations=10, robust=False,
+                                 stop=None, stop_at_check=None):
+    """LoopClosing::RunGlobalBundleAdjustment (src/LoopClosing.cc:790-901) without the thread
+    handshakes: the bundle adjustment, then, unless the stop flag was seen, the map update of
+    :812-891.  The spanning tree is walked breadth-first from `origins` (mvpKeyFrameOrigins), children
+    in ascending id: a child the bundle adjustment did not optimise takes (Tchild * Twc_parent) *
+    tcw_gba_parent; every keyframe reached keeps its pose in tcw_bef_gba and takes tcw_gba.  A point
+    that was optimised takes pos_gba; another is carried through its reference keyframe,
+    Rwc (Rcw_before X + tcw_before) + twc, unless that keyframe was not reached.  The products are
+    float with double accumulators (cv::gemm's convention here; not pinned against OpenCV).
+    loop_kf_id == 0 is BundleAdjustment's direct write-back: nothing is left to propagate.
+    -> {"ba", "applied", "optimised", "propagated", "carried", "skipped"}."""
+    from .system import _mul, pose_inverse
+    ba = global_bundle_adjustment(keyframes, map_points, loop_kf_id, backend, iterations, robust, stop, stop_at_check)
+    out = {"ba": ba, "applied": False, "optimised": 0, "propagated": 0, "carried": 0, "skipped": 0}
+    if ba["stop_check"] >= 0 or (stop is not None and stop.value):  # if(!mbStopGBA)
+        return out
+    out["applied"] = True
+    out["optimised"] = len(ba["keyframes"])
+    if loop_kf_id == 0:
+        return out
+    queue = list(origins)
+    at = 0
+    while at < len(queue):
+        kf = queue[at]
+        at += 1
+        Twc = pose_inverse(kf.tcw)
+        for child in sorted(kf.children, key=lambda k: k.id):
+            if child.ba_global_for_kf != loop_kf_id:
+                child.tcw_gba = _mul(_mul(child.tcw, Twc), kf.tcw_gba)
+                child.ba_global_for_kf = loop_kf_id
+                out["propagated"] += 1
+            queue.append(child)
+        kf.tcw_bef_gba = kf.tcw
+        kf.tcw = np.asarray(kf.tcw_gba, np.float32).reshape(4, 4).copy()
+    for mp in map_points:
+        if mp.bad:
+            continue
+        if mp.ba_global_for_kf == loop_kf_id:
+            mp.pos = np.asarray(mp.pos_gba, np.float32).copy()
+            continue
+        ref = mp.ref_kf
+        if ref is None or ref.ba_global_for_kf != loop_kf_id or ref.tcw_bef_gba is None:
+            out["skipped"] += 1
+            continue
+        Tb = np.asarray(ref.tcw_bef_gba, np.float32).reshape(4, 4)
+        Xc = (_mul(Tb[:3, :3], np.asarray(mp.pos, np.float32).reshape(3, 1)) + Tb[:3, 3:4]).astype(np.float32)
+        Twc = pose_inverse(ref.tcw)
+        mp.pos = (_mul(Twc[:3, :3], Xc) + Twc[:3, 3:4]).astype(np.float32)[:, 0].copy()
+        out["carried"] += 1
+    return out

@@ -55,6 +55,65 @@ class LocalBA:
                 "stop_check": r.stop_check, "checks": r.checks}
 
 
+class GlobalBA(LocalBA):
+    """Optimizer::BundleAdjustment (src/Optimizer.cc:56-255) over the C ABI, on an orbmi_ba handle:
+    `run` optimises a graph assembled by gather_global_ba (or any BAProblem) on the GPU."""
+
+    TERMINATE, SOLVE_FAILED, REJECTED = 1, 2, 4   # ORBMI_GBA_*
+
+    def run(self, problem: BAProblem, iterations: int = 10, robust: bool = False, stop: C.c_int | None = None,
+            stop_at_check: int | None = None):
+        from .types import GBAResultView
+        if stop_at_check is not None:
+            self.set_stop_at_check(stop_at_check)
+        n = len(problem.kfs), len(problem.pts)
+        tcw = np.zeros((max(n[0], 1), 16), np.float32)
+        pos = np.zeros((max(n[1], 1), 3), np.float32)
+        inc = np.zeros(max(n[1], 1), np.uint8)
+        r = GBAResultView(tcw.ctypes.data, pos.ctypes.data, inc.ctypes.data)
+        v = problem.view()
+        check("orbmi_bundle_adjustment",
+              lib().orbmi_bundle_adjustment(self._h, C.addressof(v), int(iterations), int(bool(robust)), C.addressof(r),
+                                            C.addressof(stop) if stop is not None else None))
+        return {"tcw": tcw[:n[0]].reshape(-1, 4, 4), "pos": pos[:n[1]], "included": inc[:n[1]].astype(bool),
+                "iterations": r.iterations, "trials": np.array(r.trials[:int(iterations)], np.int32),
+                "chi2_initial": r.chi2_initial, "chi2": r.chi2, "stop_check": r.stop_check, "checks": r.checks,
+                "status": r.status, "n_free": r.n_free, "n_blocks": r.n_blocks, "phase_ms": tuple(r.phase_ms)}
+
+
+def gather_global_ba(keyframes, map_points):
+    """The graph of Optimizer::BundleAdjustment (src/Optimizer.cc:78-200) over the minimal map
+    model: every keyframe and point that is not bad, one edge per observation in ascending keyframe
+    id (the build's replacement of pointer order), observations of bad keyframes and of keyframes
+    outside `keyframes` skipped, fixed = (id == 0).  A point left without an edge stays in the
+    arrays and comes back with included = 0.  -> (BAProblem, keyframes kept, points kept)."""
+    kfs = [k for k in keyframes if not k.bad]
+    mps = [mp for mp in map_points if not mp.bad]
+    kidx = {id(k): i for i, k in enumerate(kfs)}
+    K = np.zeros(len(kfs), BA_KF_DTYPE)
+    for i, k in enumerate(kfs):
+        K[i]["tcw"] = np.asarray(k.tcw, np.float32).reshape(-1)
+        K[i]["id"] = k.id
+        K[i]["fixed"] = 1 if k.id == 0 else 0
+        K[i]["fx"], K[i]["fy"], K[i]["cx"], K[i]["cy"], K[i]["bf"] = k.cam.fx, k.cam.fy, k.cam.cx, k.cam.cy, k.cam.bf
+    P = np.zeros(len(mps), BA_PT_DTYPE)
+    if mps:
+        P["pos"] = np.array([mp.pos for mp in mps], np.float32).reshape(-1, 3)
+        P["id"] = [mp.id for mp in mps]
+    rows = []
+    for pi, mp in enumerate(mps):
+        for kf in sorted(mp.observations, key=lambda k: k.id):
+            ki = kidx.get(id(kf))
+            if kf.bad or ki is None:
+                continue
+            j = mp.observations[kf]
+            kp = kf.keys_un[j]
+            rows.append((pi, ki, kp["x"], kp["y"], np.float32(kf.u_right[j]),
+                         np.float32(kf.inv_level_sigma2[int(kp["octave"])])))
+    E = np.array(rows, BA_EDGE_DTYPE) if rows else np.zeros(0, BA_EDGE_DTYPE)
+    return BAProblem(K, P, E), kfs, mps
+
+
 class PoseOptimizer:
     """Optimizer::PoseOptimization(Frame*) (include/Optimizer.h:58) on the GPU, batched: one
     workgroup per frame.  `run(frames, obs)` updates the POSE_FRAME_DTYPE records in place
@@ -135,6 +194,8 @@ class KeyFrame:
     map_points: list = dataclasses.field(default_factory=list)   # MapPoint or None per keypoint
     covisible: list = dataclasses.field(default_factory=list)    # GetVectorCovisibleKeyFrames order
     bad: bool = False
+    tcw_gba: np.ndarray = None          # mTcwGBA (loop.global_bundle_adjustment)
+    ba_global_for_kf: int = 0           # mnBAGlobalForKF
 
 
 @dataclasses.dataclass(eq=False)
@@ -143,6 +204,8 @@ class MapPoint:
     pos: np.ndarray
     observations: dict = dataclasses.field(default_factory=dict)  # KeyFrame -> keypoint index
     bad: bool = False
+    pos_gba: np.ndarray = None          # mPosGBA
+    ba_global_for_kf: int = 0           # mnBAGlobalForKF
 
 
 def gather_local_ba(pKF: KeyFrame):

@@ -146,6 +146,9 @@ class KeyFrame:
     fuse_target_for_kf: int = -1    # mnFuseTargetForKF
     tcp: np.ndarray = None          # mTcp (set when the keyframe turns bad)
     loop_edges: list = dataclasses.field(default_factory=list)  # mspLoopEdges (loop.correct_loop adds them)
+    tcw_gba: np.ndarray = None      # mTcwGBA (loop.global_bundle_adjustment)
+    tcw_bef_gba: np.ndarray = None  # mTcwBefGBA
+    ba_global_for_kf: int = 0       # mnBAGlobalForKF
 
     @property
     def Ow(self) -> np.ndarray:
@@ -282,6 +285,8 @@ class MapPoint:
     fuse_candidate_for_kf: int = -1  # mnFuseCandidateForKF
     corrected_by_kf: int = -1        # mnCorrectedByKF (loop.correct_loop)
     corrected_reference: int = -1    # mnCorrectedReference
+    pos_gba: np.ndarray = None       # mPosGBA (loop.global_bundle_adjustment)
+    ba_global_for_kf: int = 0        # mnBAGlobalForKF
 
     def found_ratio(self) -> np.float32:
         """MapPoint::GetFoundRatio: static_cast<float>(mnFound) / mnVisible."""

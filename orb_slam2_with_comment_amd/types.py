@@ -166,6 +166,18 @@ class BAResultView(C.Structure):
                 ("chi2", C.c_double * 2), ("aborted", C.c_int), ("stop_check", C.c_int), ("checks", C.c_int)]
 
 
+GBA_MAX_ITERATIONS = 64   # ORBMI_GBA_MAX_ITERATIONS
+GBA_MAX_FREE_POSES = 2048  # ORBMI_GBA_MAX_FREE_POSES
+
+
+class GBAResultView(C.Structure):
+    """orbmi_gba_result (include/orbmi.h)."""
+    _fields_ = [("tcw", C.c_void_p), ("pos", C.c_void_p), ("included", C.c_void_p), ("iterations", C.c_int),
+                ("trials", C.c_int * GBA_MAX_ITERATIONS), ("chi2_initial", C.c_double), ("chi2", C.c_double),
+                ("stop_check", C.c_int), ("checks", C.c_int), ("status", C.c_int), ("n_free", C.c_int),
+                ("n_blocks", C.c_int), ("phase_ms", C.c_double * 4)]
+
+
 class LMJob(C.Structure):
     """orbmi_lm_job: one LocalMapping::Run iteration for orbmi_local_mapping_job (include/orbmi.h)."""
     _fields_ = [("voc", C.c_void_p), ("bow_desc", C.c_void_p), ("bow_n", C.c_int), ("bow_word", C.c_void_p),
