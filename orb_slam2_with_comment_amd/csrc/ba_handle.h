@@ -6,7 +6,25 @@
 
 namespace orbmi {
 struct BaCtl;
-}
+
+// the caller's stop flag (bool* pbStopFlag, src/Optimizer.cc:483), written by other threads:
+// read with an atomic load
+inline bool stop_set(const volatile int* stop) { return stop && __atomic_load_n(stop, __ATOMIC_ACQUIRE) != 0; }
+
+// The slots of a device arena, listed once and walked twice: with base null the walk sums the
+// sizes (every slot 256-aligned, 8 bytes at least), with the arena's address it binds the
+// pointers.  A slot is the pointer, whose type gives the element size, and the element count.
+struct ArenaWalk {
+    uint8_t* base = nullptr;
+    size_t off = 0;
+    template <class T>
+    void operator()(T*& p, size_t n) {
+        if (base) p = (T*)(base + off);
+        const size_t bytes = n * sizeof(T);
+        off += ((bytes < 8 ? 8 : bytes) + 255) & ~(size_t)255;
+    }
+};
+}  // namespace orbmi
 
 struct orbmi_ba {
     int device = 0;

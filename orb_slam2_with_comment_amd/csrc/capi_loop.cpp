@@ -416,28 +416,6 @@ int essgraph_stage(Stage& s, const orbmi_essgraph_problem& P, const std::vector<
     return ORBMI_OK;
 }
 
-// HIP events around one phase of a profiled call
-struct EssgraphTimer {
-    Matcher& m;
-    bool on;
-    hipEvent_t a = nullptr, b = nullptr;
-    EssgraphTimer(Matcher& m_, bool on_) : m(m_), on(on_) {
-        if (on && (hipEventCreate(&a) != hipSuccess || hipEventCreate(&b) != hipSuccess)) on = false;
-    }
-    ~EssgraphTimer() {
-        if (a) (void)hipEventDestroy(a);
-        if (b) (void)hipEventDestroy(b);
-    }
-    void begin() { if (on) (void)hipEventRecord(a, m.ls()); }
-    void end(float* acc) {
-        if (!on) return;
-        float ms = 0;
-        if (hipEventRecord(b, m.ls()) == hipSuccess && hipEventSynchronize(b) == hipSuccess &&
-            hipEventElapsedTime(&ms, a, b) == hipSuccess)
-            *acc += ms;
-    }
-};
-
 }  // namespace
 
 extern "C" {
@@ -494,7 +472,7 @@ int orbmi_optimize_essential_graph(orbmi_matcher* h, const orbmi_essgraph_proble
         return ORBMI_OK;
     }
     const orbmi::EgDev& D = C.D;
-    EssgraphTimer T(m, P.profile != 0);
+    orbmi::PhaseTimer T(m.ls(), P.profile != 0);
     orbmi::S3oLm L{};
     double out[orbmi::kEgOut];
     auto read_out = [&]() -> int {
@@ -512,7 +490,7 @@ int orbmi_optimize_essential_graph(orbmi_matcher* h, const orbmi_essgraph_proble
         T.end(&R.phase_ms[1]);
         if ((rc = read_out())) return rc;
         if (it == 0) R.chi2_before = out[orbmi::kEgOutChi];
-        orbmi::eg_lm_begin(L, it, out[orbmi::kEgOutChi]);
+        orbmi::lm_begin(L, it, out[orbmi::kEgOutChi], [] { return orbmi::kEgLambdaInit; });
         bool more;
         do {
             T.begin();
@@ -531,12 +509,12 @@ int orbmi_optimize_essential_graph(orbmi_matcher* h, const orbmi_essgraph_proble
             } else {
                 R.status |= ORBMI_EG_SOLVE_FAILED;
             }
-            if (orbmi::eg_lm_trial(L, ok2, tempChi, scale, &more)) std::swap(C.est, C.trial);  // the step is kept
+            if (orbmi::lm_trial(L, ok2, tempChi, scale, &more, orbmi::LmCubeMul())) std::swap(C.est, C.trial);  // the step is kept
             else R.status |= ORBMI_EG_REJECTED;  // est still holds the accepted estimates
         } while (more);
         R.trials[it] = L.qmax;
         R.iterations++;
-        if (orbmi::s3o_lm_end(L)) {
+        if (orbmi::lm_end(L)) {
             stopped = true;
             break;
         }

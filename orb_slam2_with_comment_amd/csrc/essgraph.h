@@ -6,6 +6,7 @@
 //   BaseBinaryEdge::linearizeOplus (numeric)       core/base_binary_edge.hpp:130-205
 //   BaseBinaryEdge::constructQuadraticForm         core/base_binary_edge.hpp:91-113
 //   OptimizationAlgorithmLevenberg::solve          core/optimization_algorithm_levenberg.cpp:61-164
+//                                                  (the decision itself: g2o_lm.h)
 // on top of sim3_opt.h's Sim3(Vector7d), operator*, inverse, map and oplusImpl.  All fp64, one
 // rounding per operation in the order written (-ffp-contract=off).  sin, cos, acos, log and exp
 // come from the platform, so host and device agree to rounding, not bit for bit.
@@ -150,41 +151,9 @@ S3O_FN double eg_chi2(const double* e) {
     return c;
 }
 
-// One trial's verdict over the whole graph (s3o_lm_trial with computeScale's sum handed in):
-// true = the step is kept.  scale_sum = sum x (lambda x + b) over every free vertex.
-S3O_FN bool eg_lm_trial(S3oLm& L, bool ok2, double tempChi, double scale_sum, bool* more) {
-    if (!ok2) tempChi = 1.7976931348623157e308;
-    const double scale = scale_sum + 1e-3;
-    L.rho = (L.currentChi - tempChi) / scale;
-    const bool accept = L.rho > 0 && tempChi - tempChi == 0;  // isfinite
-    if (accept) {
-        const double z = 2 * L.rho - 1;
-        double alpha = 1. - z * z * z;
-        alpha = alpha < 2. / 3. ? alpha : 2. / 3.;
-        L.lambda = L.lambda * (1. / 3. > alpha ? 1. / 3. : alpha);
-        L.ni = 2;
-        L.currentChi = tempChi;
-    } else {
-        L.lambda = L.lambda * L.ni;
-        L.ni = L.ni * 2;
-    }
-    L.qmax++;
-    *more = L.rho < 0 && L.qmax < kS3oMaxTrials;
-    return accept;
-}
-
-// After buildSystem of iteration `it`: setUserLambdaInit(1e-16)
-S3O_FN void eg_lm_begin(S3oLm& L, int it, double chi) {
-    L.currentChi = chi;
-    L.iniChi = chi;
-    if (it == 0) {
-        L.lambda = 1e-16;
-        L.ni = 2;
-        L.nBad = 0;
-    }
-    L.rho = 0;
-    L.qmax = 0;
-}
+// The Levenberg decision is g2o_lm.h's, with setUserLambdaInit(1e-16), computeScale's sum over every
+// free vertex handed in, and the cube of sim3_opt.h (z * z * z)
+constexpr double kEgLambdaInit = 1e-16;
 
 // CorrectLoop's pose recovery (src/LoopClosing.cc:620-628, src/Optimizer.cc:1069-1079):
 // [R | t * (1. / s)] as a float 4x4 Tcw
@@ -569,7 +538,7 @@ inline EgHostResult eg_optimize_host(int nv, int fixed, int ne, const EgEdge* ed
     for (int it = 0; it < iterations; it++) {
         eg_build_host(P, edges, est, fix_scale, &Y);
         if (it == 0) R.chi2_before = Y.chi2;
-        eg_lm_begin(L, it, Y.chi2);
+        lm_begin(L, it, Y.chi2, [] { return kEgLambdaInit; });
         bool more;
         do {
             const bool ok2 = eg_solve_host(P, Y, L.lambda, &x);
@@ -585,7 +554,7 @@ inline EgHostResult eg_optimize_host(int nv, int fixed, int ne, const EgEdge* ed
             } else {
                 R.status |= kEgSolveFailed;
             }
-            if (eg_lm_trial(L, ok2, tempChi, scale, &more)) {
+            if (lm_trial(L, ok2, tempChi, scale, &more, LmCubeMul())) {
                 for (int c = 0; c < P.nf; c++) est[P.vert_of[c]] = trial[P.vert_of[c]];
             } else {
                 R.status |= kEgRejected;
@@ -593,7 +562,7 @@ inline EgHostResult eg_optimize_host(int nv, int fixed, int ne, const EgEdge* ed
         } while (more);
         R.trials[it] = L.qmax;
         R.iterations++;
-        if (s3o_lm_end(L)) {
+        if (lm_end(L)) {
             stopped = true;
             break;
         }

@@ -86,23 +86,10 @@ __global__ __launch_bounds__(64) void k_eg_assemble(EgDev D) {
     else D.Ho[(size_t)(s - D.nf) * 49 + q] = v;
 }
 
-// The sum of n values `stride` apart in one workgroup: thread t adds t, t + 256, ... in that order,
-// then a fixed tree, so the result does not depend on the launch
-__device__ __forceinline__ double eg_block_sum(double part, double* red) {
-    red[threadIdx.x] = part;
-    __syncthreads();
-    for (int s = kEgThreads / 2; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) red[threadIdx.x] = red[threadIdx.x] + red[threadIdx.x + s];
-        __syncthreads();
-    }
-    return red[0];
-}
-
+// The sum of n values `stride` apart in one workgroup, in wave_ops.h's fixed order
 __global__ __launch_bounds__(kEgThreads) void k_eg_reduce(const double* __restrict__ src, int n, int stride, double* __restrict__ dst) {
     __shared__ double red[kEgThreads];
-    double part = 0;
-    for (int i = threadIdx.x; i < n; i += kEgThreads) part = part + src[(size_t)i * stride];
-    const double t = eg_block_sum(part, red);
+    const double t = strided_sum_fixed<kEgThreads>(src, n, stride, red);
     if (threadIdx.x == 0) *dst = t;
 }
 
@@ -202,7 +189,7 @@ __global__ __launch_bounds__(kEgThreads) void k_eg_factor_solve(EgDev D, double 
     }
     double part = 0;  // computeScale: sum x (lambda x + b)
     for (int i = tid; i < nf * 7; i += kEgThreads) part = part + D.x[i] * (lambda * D.x[i] + D.b[i]);
-    const double t = eg_block_sum(part, red);
+    const double t = block_sum_fixed<kEgThreads>(part, red);
     if (tid == 0) {
         D.out[kEgOutScale] = t;
         D.out[kEgOutFail] = fail ? 1.0 : 0.0;

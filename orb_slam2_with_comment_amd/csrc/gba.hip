@@ -2,7 +2,8 @@
 // over any number of keyframes.
 //
 // One SparseOptimizer::optimize(n) with OptimizationAlgorithmLevenberg over BlockSolver_6_3.  The
-// Levenberg decisions are taken on the host from one small read-back per trial; the
+// Levenberg decisions are taken on the host from one small read-back per trial, by
+// g2o_lm.h; the graph's index tables and pair lists are ba_graph.h's, shared with LocalBA; the
 // arithmetic runs in these kernels, all on the handle's stream:
 //   per iteration
 //     k_gba_linearize  thread / edge    error, robust chi2, Jacobians, the edge's blocks (ba_edge.h)
@@ -24,14 +25,14 @@
 // Compiled under the build's -ffp-contract=off; no floating-point atomics; every sum has a fixed
 // order, so two calls return the same bits.
 #include <algorithm>
-#include <cfloat>
 #include <cmath>
 #include <cstdlib>
-#include <cstring>
 #include <vector>
 
 #include "ba_edge.h"
+#include "ba_graph.h"
 #include "ba_handle.h"
+#include "g2o_lm.h"
 
 namespace orbmi {
 
@@ -151,29 +152,14 @@ __global__ __launch_bounds__(kGbaThreads) void k_gba_reduce(GbaDev a) {
         if (q == upper6(d, d)) a.vmax[6 * (size_t)i + d] = fabs(s);
 }
 
-__device__ __forceinline__ double gba_block_sum(double part, double* red) {
-    red[threadIdx.x] = part;
-    __syncthreads();
-    for (int s = kGbaThreads / 2; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) red[threadIdx.x] = red[threadIdx.x] + red[threadIdx.x + s];
-        __syncthreads();
-    }
-    return red[0];
-}
-
 // computeLambdaInit's max |diag H| (a maximum does not depend on the order)
 __global__ __launch_bounds__(kGbaThreads) void k_gba_max(GbaDev a) {
     __shared__ double red[kGbaThreads];
     double m = 0;
     const long long n = 6LL * a.nf + a.npt;
     for (long long i = threadIdx.x; i < n; i += kGbaThreads) m = fmax(m, a.vmax[i]);
-    red[threadIdx.x] = m;
-    __syncthreads();
-    for (int s = kGbaThreads / 2; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) red[threadIdx.x] = fmax(red[threadIdx.x], red[threadIdx.x + s]);
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) a.out[kGbaOutMax] = red[0];
+    m = block_reduce_fixed<kGbaThreads>(m, red, [](double x, double y) { return fmax(x, y); });
+    if (threadIdx.x == 0) a.out[kGbaOutMax] = m;
 }
 
 // block 0: the chi2 of the edges; block 1: computeScale over every free vertex
@@ -181,9 +167,7 @@ __global__ __launch_bounds__(kGbaThreads) void k_gba_sum(GbaDev a) {
     __shared__ double red[kGbaThreads];
     const double* src = blockIdx.x == 0 ? a.chi_e : a.sc;
     const long long n = blockIdx.x == 0 ? a.ne : (long long)a.nf + a.npt;
-    double part = 0;
-    for (long long i = threadIdx.x; i < n; i += kGbaThreads) part = part + src[i];
-    const double t = gba_block_sum(part, red);
+    const double t = strided_sum_fixed<kGbaThreads>(src, n, 1, red);
     if (threadIdx.x == 0) a.out[blockIdx.x == 0 ? kGbaOutChi : kGbaOutScale] = t;
 }
 
@@ -436,66 +420,9 @@ __global__ __launch_bounds__(kGbaThreads) void k_gba_finish(GbaDev a, const doub
 
 }  // namespace orbmi
 
-namespace {
-
 using namespace orbmi;
 
-inline bool gba_stop_set(const volatile int* stop) { return stop && *stop; }
-
-// The host-built index tables against the lengths of the arrays they address (before any launch)
-bool gba_plan_ok(int nkf, int npt, int ne, int nf, const std::vector<int>& pt_start, const std::vector<int>& kf_start,
-                 const std::vector<int>& kf_edges, const std::vector<int>& kf_pos, const std::vector<int>& rank,
-                 const std::vector<int>& free_kf, const std::vector<int>& blk_ij, const std::vector<int>& blk_start,
-                 const std::vector<int2>& pairs) {
-    if ((int)pt_start.size() != npt + 1 || (int)kf_start.size() != nkf + 1 || pt_start[0] != 0 || kf_start[0] != 0 ||
-        pt_start[npt] != ne || kf_start[nkf] != ne)
-        return false;
-    for (int p = 0; p < npt; p++)
-        if (pt_start[p] > pt_start[p + 1]) return false;
-    for (int k = 0; k < nkf; k++)
-        if (kf_start[k] > kf_start[k + 1]) return false;
-    if ((int)kf_edges.size() != ne || (int)kf_pos.size() != ne || (int)rank.size() != nkf || (int)free_kf.size() != nf)
-        return false;
-    for (int e = 0; e < ne; e++)
-        if (kf_edges[e] < 0 || kf_edges[e] >= ne || kf_pos[e] < 0 || kf_pos[e] >= ne) return false;
-    for (int k = 0; k < nkf; k++)
-        if (rank[k] < -1 || rank[k] >= nf) return false;
-    for (int i = 0; i < nf; i++)
-        if (free_kf[i] < 0 || free_kf[i] >= nkf || rank[free_kf[i]] != i) return false;
-    const int nblk = (int)blk_ij.size() / 2;
-    if ((int)blk_start.size() != nblk + 1 || blk_start[0] != 0 || blk_start[nblk] != (int)pairs.size()) return false;
-    for (int b = 0; b < nblk; b++) {
-        const int i = blk_ij[2 * b], j = blk_ij[2 * b + 1];
-        if (i < 0 || i >= nf || j < 0 || j > i || blk_start[b] > blk_start[b + 1]) return false;
-    }
-    for (const int2& p : pairs)
-        if (p.x < 0 || p.x >= ne || p.y < 0 || p.y >= ne) return false;
-    return true;
-}
-
-struct GbaPhase {  // ORBMI_GBA_PROFILE=1: the phases' device time (a synchronisation per phase)
-    bool on;
-    hipStream_t s;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    double ms[4] = {0, 0, 0, 0};
-    GbaPhase(bool o, hipStream_t st) : on(o), s(st) {
-        if (on && (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess)) on = false;
-    }
-    ~GbaPhase() {
-        if (e0) (void)hipEventDestroy(e0);
-        if (e1) (void)hipEventDestroy(e1);
-    }
-    void begin() { if (on) (void)hipEventRecord(e0, s); }
-    void end(int k) {
-        if (!on) return;
-        float t = 0;
-        if (hipEventRecord(e1, s) == hipSuccess && hipEventSynchronize(e1) == hipSuccess &&
-            hipEventElapsedTime(&t, e0, e1) == hipSuccess)
-            ms[k] += t;
-    }
-};
-
-}  // namespace
+static_assert(sizeof(BaPair) == sizeof(int2) && alignof(BaPair) <= alignof(int2), "BaPair goes up as the kernels' int2");
 
 extern "C" int orbmi_bundle_adjustment(orbmi_ba* b, const orbmi_ba_problem* P, int iterations, int robust,
                                        orbmi_gba_result* R, const volatile int* stop) {
@@ -504,75 +431,21 @@ extern "C" int orbmi_bundle_adjustment(orbmi_ba* b, const orbmi_ba_problem* P, i
     if ((P->nkf && (!P->kfs || !R->tcw)) || (P->npt && (!P->pts || !R->pos || !R->included)) || (P->nedge && !P->edges))
         return ORBMI_E_ARG;
     const int nkf = P->nkf, npt = P->npt, ne = P->nedge;
-    // ---- the graph's index tables, on the host
-    {
-        std::vector<int> last_pt(std::max(nkf, 1), -1);
-        for (int i = 0; i < ne; i++) {
-            const orbmi_ba_edge& e = P->edges[i];
-            if (e.point < 0 || e.point >= npt || e.kf < 0 || e.kf >= nkf) return ORBMI_E_ARG;
-            if (i && e.point < P->edges[i - 1].point) return ORBMI_E_ARG;  // grouped by point
-            if (last_pt[e.kf] == e.point) return ORBMI_E_ARG;              // one edge per (point, keyframe)
-            last_pt[e.kf] = e.point;
-        }
-    }
-    std::vector<int> pt_start(npt + 1, 0), kf_start(nkf + 1, 0), kf_edges(ne), kf_pos(ne), rank(nkf, -1), free_kf;
-    for (int i = 0; i < ne; i++) { pt_start[P->edges[i].point + 1]++; kf_start[P->edges[i].kf + 1]++; }
-    for (int p = 0; p < npt; p++) pt_start[p + 1] += pt_start[p];
-    for (int k = 0; k < nkf; k++) kf_start[k + 1] += kf_start[k];
-    {
-        std::vector<int> fill(kf_start.begin(), kf_start.end() - 1);
-        for (int i = 0; i < ne; i++) {
-            const int j = fill[P->edges[i].kf]++;
-            kf_pos[i] = j;
-            kf_edges[j] = i;
-        }
-    }
-    // pose blocks in vertex (id) order: the free keyframes that an edge names
-    {
-        std::vector<int> order(nkf);
-        for (int k = 0; k < nkf; k++) order[k] = k;
-        std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return P->kfs[x].id < P->kfs[y].id; });
-        for (int k : order)
-            if (!P->kfs[k].fixed && kf_start[k + 1] > kf_start[k]) { rank[k] = (int)free_kf.size(); free_kf.push_back(k); }
-    }
-    const int nf = (int)free_kf.size();
+    // ---- the plan (ba_graph.h): the graph's index tables, the pose blocks in vertex (id) order --
+    // the free keyframes that an edge names -- and the pair lists of the non-zero blocks of S
+    std::vector<int> pt_start(npt + 1), kf_start(nkf + 1), kf_edges(ne), kf_pos(ne), order(nkf), rank(nkf), free_kf(nkf);
+    int rc = ba_graph_index(*P, pt_start.data(), kf_start.data(), kf_edges.data(), kf_pos.data(), nullptr);
+    if (rc) return rc;  // ORBMI_E_ARG: the edges' validation
+    const int nf = ba_graph_rank(*P, kf_start.data(), order.data(), rank.data(), free_kf.data());
     if (nf > kGbaMaxFreePoses) return ORBMI_E_UNSUPPORTED;
-    // the pair lists of the non-zero blocks of S (i >= j), pairs in point order
-    long long npair_ll = 0;
-    for (int p = 0; p < npt; p++) {
-        long long m = 0;
-        for (int e = pt_start[p]; e < pt_start[p + 1]; e++) m += rank[P->edges[e].kf] >= 0;
-        npair_ll += m * (m + 1) / 2;
-    }
-    if (npair_ll > kGbaMaxPairs) return ORBMI_E_UNSUPPORTED;
-    struct Pair { long long key; int ea, eb; };
-    std::vector<Pair> pl;
-    pl.reserve((size_t)npair_ll);
-    for (int p = 0; p < npt; p++)
-        for (int e1 = pt_start[p]; e1 < pt_start[p + 1]; e1++) {
-            const int r1 = rank[P->edges[e1].kf];
-            if (r1 < 0) continue;
-            for (int e2 = pt_start[p]; e2 < pt_start[p + 1]; e2++) {
-                const int r2 = rank[P->edges[e2].kf];
-                if (r2 < 0 || r2 > r1) continue;
-                pl.push_back(Pair{(long long)r1 * (r1 + 1) / 2 + r2, e1, e2});
-            }
-        }
-    std::stable_sort(pl.begin(), pl.end(), [](const Pair& x, const Pair& y) { return x.key < y.key; });
+    const long long npair = gba_pair_count(*P, pt_start.data(), rank.data());
+    if (npair > kGbaMaxPairs) return ORBMI_E_UNSUPPORTED;
     std::vector<int> blk_ij, blk_start;
-    std::vector<int2> pairs(pl.size());
-    for (size_t t = 0; t < pl.size(); t++) {
-        if (t == 0 || pl[t].key != pl[t - 1].key) {
-            blk_ij.push_back(rank[P->edges[pl[t].ea].kf]);
-            blk_ij.push_back(rank[P->edges[pl[t].eb].kf]);
-            blk_start.push_back((int)t);
-        }
-        pairs[t] = int2{pl[t].ea, pl[t].eb};
-    }
-    blk_start.push_back((int)pl.size());
-    std::vector<Pair>().swap(pl);
+    std::vector<BaPair> pairs;
+    gba_pair_lists(*P, pt_start.data(), rank.data(), npair, &blk_ij, &blk_start, &pairs);
     const int nblk = (int)blk_ij.size() / 2;
-    if (!gba_plan_ok(nkf, npt, ne, nf, pt_start, kf_start, kf_edges, kf_pos, rank, free_kf, blk_ij, blk_start, pairs))
+    if (!gba_plan_ok(*P, nf, pt_start.data(), kf_start.data(), kf_edges.data(), kf_pos.data(), rank.data(), free_kf.data(),
+                     blk_ij, blk_start, pairs))
         return ORBMI_E_ARG;
     const int N = 6 * nf, Npad = (N + kGbaPanel - 1) / kGbaPanel * kGbaPanel, NT = Npad / kGbaTile, npanel = Npad / kGbaPanel;
 
@@ -580,76 +453,53 @@ extern "C" int orbmi_bundle_adjustment(orbmi_ba* b, const orbmi_ba_problem* P, i
     ORBMI_HIP(hipSetDevice(h.device));
     hipStream_t s = h.stream;
     if (!h.h_gba) ORBMI_HIP(hipHostMalloc((void**)&h.h_gba, sizeof(double) * kGbaOutN));
-    // ---- one device arena, sized from the problem
-    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off += al(std::max(bytes, (size_t)8)); return o; };
-    const size_t ntiles = gba_tile(NT, NT) + 1;  // the lower triangle and the extra tile row
-    const size_t o_kfs = take(sizeof(orbmi_ba_keyframe) * nkf), o_pts = take(sizeof(orbmi_ba_point) * npt),
-                 o_edges = take(sizeof(orbmi_ba_edge) * (size_t)ne), o_pt_start = take(4 * ((size_t)npt + 1)),
-                 o_kf_start = take(4 * ((size_t)nkf + 1)), o_kf_edges = take(4 * (size_t)ne), o_kf_pos = take(4 * (size_t)ne),
-                 o_rank = take(4 * (size_t)nkf), o_free = take(4 * (size_t)nf), o_blk_ij = take(8 * (size_t)nblk),
-                 o_blk_start = take(4 * ((size_t)nblk + 1)), o_pairs = take(8 * pairs.size());
-    const size_t o_T0 = take(64 * (size_t)nkf), o_T1 = take(64 * (size_t)nkf), o_X0 = take(32 * (size_t)npt),
-                 o_X1 = take(32 * (size_t)npt), o_Hpl = take(144 * (size_t)ne), o_Hle = take(72 * (size_t)ne),
-                 o_Hpe = take(216 * (size_t)ne), o_Hll = take(72 * (size_t)npt), o_bl = take(24 * (size_t)npt),
-                 o_Hpp = take(216 * (size_t)nf), o_Dinv = take(72 * (size_t)npt), o_db = take(24 * (size_t)npt),
-                 o_Y = take(144 * (size_t)ne), o_vmax = take(8 * (6 * (size_t)nf + npt)), o_S = take(2048 * ntiles),
-                 o_dinv = take(8 * (size_t)Npad), o_Wb = take(8 * (size_t)kGbaPanel * (Npad + kGbaTile)),
-                 o_Lb = take(8 * (size_t)kGbaPanel * (Npad + kGbaTile)), o_x = take(8 * (size_t)Npad),
-                 o_sc = take(8 * ((size_t)nf + npt)), o_chi = take(8 * (size_t)ne), o_out = take(8 * kGbaOutN),
-                 o_otcw = take(64 * (size_t)nkf), o_opos = take(12 * (size_t)npt), o_oinc = take((size_t)npt);
-    ORBMI_HIP(hipStreamSynchronize(s));
-    if (off > h.cap) {
-        if (h.d_buf) (void)hipFree(h.d_buf);
-        h.d_buf = nullptr;
-        h.cap = 0;
-        ORBMI_HIP(hipMalloc((void**)&h.d_buf, off));
-        h.cap = off;
-    }
-    uint8_t* B = h.d_buf;
-    auto up = [&](size_t o, const void* src, size_t bytes) {
-        return bytes ? hipMemcpyAsync(B + o, src, bytes, hipMemcpyHostToDevice, s) : hipSuccess;
-    };
-    ORBMI_HIP(up(o_kfs, P->kfs, sizeof(orbmi_ba_keyframe) * nkf));
-    ORBMI_HIP(up(o_pts, P->pts, sizeof(orbmi_ba_point) * npt));
-    ORBMI_HIP(up(o_edges, P->edges, sizeof(orbmi_ba_edge) * (size_t)ne));
-    ORBMI_HIP(up(o_pt_start, pt_start.data(), 4 * ((size_t)npt + 1)));
-    ORBMI_HIP(up(o_kf_start, kf_start.data(), 4 * ((size_t)nkf + 1)));
-    ORBMI_HIP(up(o_kf_edges, kf_edges.data(), 4 * (size_t)ne));
-    ORBMI_HIP(up(o_kf_pos, kf_pos.data(), 4 * (size_t)ne));
-    ORBMI_HIP(up(o_rank, rank.data(), 4 * (size_t)nkf));
-    ORBMI_HIP(up(o_free, free_kf.data(), 4 * (size_t)nf));
-    ORBMI_HIP(up(o_blk_ij, blk_ij.data(), 8 * (size_t)nblk));
-    ORBMI_HIP(up(o_blk_start, blk_start.data(), 4 * ((size_t)nblk + 1)));
-    ORBMI_HIP(up(o_pairs, pairs.data(), 8 * pairs.size()));
-    ORBMI_HIP(hipStreamSynchronize(s));  // the pageable sources have been read
-
+    // ---- one device arena, sized from the problem: every slot once (ArenaWalk)
     GbaDev a;
     a.nkf = nkf; a.npt = npt; a.ne = ne; a.nf = nf; a.nblk = nblk;
     a.N = N; a.Npad = Npad; a.NT = NT;
     a.robust = robust ? 1 : 0;
-    a.kfs = (const orbmi_ba_keyframe*)(B + o_kfs);
-    a.pts = (const orbmi_ba_point*)(B + o_pts);
-    a.edges = (const orbmi_ba_edge*)(B + o_edges);
-    a.pt_start = (const int*)(B + o_pt_start); a.kf_start = (const int*)(B + o_kf_start);
-    a.kf_edges = (const int*)(B + o_kf_edges); a.kf_pos = (const int*)(B + o_kf_pos);
-    a.rank = (const int*)(B + o_rank); a.free_kf = (const int*)(B + o_free);
-    a.blk_ij = (const int*)(B + o_blk_ij); a.blk_start = (const int*)(B + o_blk_start);
-    a.blk_pairs = (const int2*)(B + o_pairs);
-    a.Hpl = (double*)(B + o_Hpl); a.Hle = (double*)(B + o_Hle); a.Hpe = (double*)(B + o_Hpe);
-    a.Hll = (double*)(B + o_Hll); a.bl = (double*)(B + o_bl); a.Hpp = (double*)(B + o_Hpp);
-    a.Dinv = (double*)(B + o_Dinv); a.db = (double*)(B + o_db); a.Y = (double*)(B + o_Y);
-    a.vmax = (double*)(B + o_vmax); a.S = (double*)(B + o_S); a.dinv = (double*)(B + o_dinv);
-    a.Wb = (double*)(B + o_Wb); a.Lb = (double*)(B + o_Lb); a.x = (double*)(B + o_x);
-    a.sc = (double*)(B + o_sc); a.chi_e = (double*)(B + o_chi); a.out = (double*)(B + o_out);
-    double* Tb[2] = {(double*)(B + o_T0), (double*)(B + o_T1)};
-    double* Xb[2] = {(double*)(B + o_X0), (double*)(B + o_X1)};
+    double *Tb[2], *Xb[2];
+    float *o_tcw, *o_pos;
+    uint8_t* o_inc;
+    const size_t ntiles = gba_tile(NT, NT) + 1;  // the lower triangle and the extra tile row
+    const size_t nE = (size_t)ne, nP = (size_t)npt, nK = (size_t)nkf, nF = (size_t)nf, nrow = (size_t)Npad + kGbaTile;
+    auto slots = [&](ArenaWalk& A) {
+        A(a.kfs, nK); A(a.pts, nP); A(a.edges, nE); A(a.pt_start, nP + 1); A(a.kf_start, nK + 1); A(a.kf_edges, nE);
+        A(a.kf_pos, nE); A(a.rank, nK); A(a.free_kf, nF); A(a.blk_ij, 2 * (size_t)nblk); A(a.blk_start, (size_t)nblk + 1);
+        A(a.blk_pairs, pairs.size());
+        A(Tb[0], 8 * nK); A(Tb[1], 8 * nK); A(Xb[0], 4 * nP); A(Xb[1], 4 * nP); A(a.Hpl, 18 * nE); A(a.Hle, 9 * nE);
+        A(a.Hpe, 27 * nE); A(a.Hll, 9 * nP); A(a.bl, 3 * nP); A(a.Hpp, 27 * nF); A(a.Dinv, 9 * nP); A(a.db, 3 * nP);
+        A(a.Y, 18 * nE); A(a.vmax, 6 * nF + nP); A(a.S, 256 * ntiles); A(a.dinv, (size_t)Npad); A(a.Wb, kGbaPanel * nrow);
+        A(a.Lb, kGbaPanel * nrow); A(a.x, (size_t)Npad); A(a.sc, nF + nP); A(a.chi_e, nE); A(a.out, (size_t)kGbaOutN);
+        A(o_tcw, 16 * nK); A(o_pos, 3 * nP); A(o_inc, nP);
+    };
+    ArenaWalk size;
+    slots(size);
+    ORBMI_HIP(hipStreamSynchronize(s));
+    if (size.off > h.cap) {
+        if (h.d_buf) (void)hipFree(h.d_buf);
+        h.d_buf = nullptr;
+        h.cap = 0;
+        ORBMI_HIP(hipMalloc((void**)&h.d_buf, size.off));
+        h.cap = size.off;
+    }
+    ArenaWalk bind{h.d_buf};
+    slots(bind);
+    const struct { const void *dst, *src; size_t bytes; } ups[] = {
+        {a.kfs, P->kfs, sizeof(orbmi_ba_keyframe) * nK}, {a.pts, P->pts, sizeof(orbmi_ba_point) * nP},
+        {a.edges, P->edges, sizeof(orbmi_ba_edge) * nE}, {a.pt_start, pt_start.data(), 4 * (nP + 1)},
+        {a.kf_start, kf_start.data(), 4 * (nK + 1)}, {a.kf_edges, kf_edges.data(), 4 * nE}, {a.kf_pos, kf_pos.data(), 4 * nE},
+        {a.rank, rank.data(), 4 * nK}, {a.free_kf, free_kf.data(), 4 * nF}, {a.blk_ij, blk_ij.data(), 8 * (size_t)nblk},
+        {a.blk_start, blk_start.data(), 4 * ((size_t)nblk + 1)}, {a.blk_pairs, pairs.data(), 8 * pairs.size()}};
+    for (const auto& u : ups)
+        if (u.bytes) ORBMI_HIP(hipMemcpyAsync(const_cast<void*>(u.dst), u.src, u.bytes, hipMemcpyHostToDevice, s));
+    ORBMI_HIP(hipStreamSynchronize(s));  // the pageable sources have been read
     int cur = 0;
 
     auto blocks = [](long long n, int per) { return dim3((unsigned)std::max(1LL, (n + per - 1) / per)); };
     const int nmax = std::max(std::max(nkf, npt), ne);
-    GbaPhase ph(getenv("ORBMI_GBA_PROFILE") != nullptr, s);
+    PhaseTimer ph(s, getenv("ORBMI_GBA_PROFILE") != nullptr);  // the phases' device time (a synchronisation per phase)
+    double phase_ms[4] = {0, 0, 0, 0};  // (into the result on success only)
     ORBMI_HIP(hipMemsetAsync(a.out, 0, 8 * kGbaOutN, s));
     hipLaunchKernelGGL(k_gba_setup, blocks(nmax, kGbaThreads), dim3(kGbaThreads), 0, s, a, Tb[0], Tb[1], Xb[0], Xb[1]);
     ORBMI_HIP(hipGetLastError());
@@ -667,7 +517,7 @@ extern "C" int orbmi_bundle_adjustment(orbmi_ba* b, const orbmi_ba_problem* P, i
         hipLaunchKernelGGL(k_gba_max, dim3(1), dim3(kGbaThreads), 0, s, a);
         hipLaunchKernelGGL(k_gba_sum, dim3(1), dim3(kGbaThreads), 0, s, a);  // block 0 only: the chi2
         ORBMI_HIP(hipGetLastError());
-        ph.end(0);
+        ph.end(&phase_ms[0]);
         return (int)ORBMI_OK;
     };
     // one trial: solve at lambda, update into the other buffers, chi2 and computeScale there
@@ -677,7 +527,7 @@ extern "C" int orbmi_bundle_adjustment(orbmi_ba* b, const orbmi_ba_problem* P, i
         hipLaunchKernelGGL(k_gba_prep, blocks(std::max(npt, Npad - N), kGbaThreads), dim3(kGbaThreads), 0, s, a, lam);
         if (nblk) hipLaunchKernelGGL(k_gba_schur, dim3(nblk), dim3(64), 0, s, a, lam);
         ORBMI_HIP(hipGetLastError());
-        ph.end(1);
+        ph.end(&phase_ms[1]);
         ph.begin();
         for (int k = 0; k < npanel; k++) {
             hipLaunchKernelGGL(k_gba_panel, dim3(1), dim3(kGbaThreads), 0, s, a, k);
@@ -689,7 +539,7 @@ extern "C" int orbmi_bundle_adjustment(orbmi_ba* b, const orbmi_ba_problem* P, i
         for (int k = npanel - 1; k >= 0; k--)
             hipLaunchKernelGGL(k_gba_back, blocks(kGbaPanel * k, kGbaRowsThreads), dim3(kGbaRowsThreads), 0, s, a, k);
         ORBMI_HIP(hipGetLastError());
-        ph.end(2);
+        ph.end(&phase_ms[2]);
         ph.begin();
         hipLaunchKernelGGL(k_gba_update, blocks(std::max(nf, npt), kGbaThreads), dim3(kGbaThreads), 0, s, a, lam,
                            (const double*)Tb[cur], (const double*)Xb[cur], Tb[cur ^ 1], Xb[cur ^ 1]);
@@ -697,70 +547,47 @@ extern "C" int orbmi_bundle_adjustment(orbmi_ba* b, const orbmi_ba_problem* P, i
                                    (const double*)Xb[cur ^ 1]);
         hipLaunchKernelGGL(k_gba_sum, dim3(2), dim3(kGbaThreads), 0, s, a);
         ORBMI_HIP(hipGetLastError());
-        ph.end(3);
+        ph.end(&phase_ms[3]);
         return (int)ORBMI_OK;
     };
 
-    // ---- SparseOptimizer::optimize(iterations) with OptimizationAlgorithmLevenberg::solve, as
-    // oracle/lba_oracle.cpp:333-391 restates them
-    int checks = 0, stop_seen = -1, status = 0, it = 0, rc;
+    // ---- SparseOptimizer::optimize(iterations) with OptimizationAlgorithmLevenberg::solve
+    // (g2o_lm.h, with g2o's own std::pow cube), as oracle/lba_oracle.cpp:333-391 restates them
+    int checks = 0, stop_seen = -1, status = 0, it = 0;
     auto terminate = [&]() {
         const int idx = checks++;
-        const bool st = gba_stop_set(stop) || (h.stop_at >= 0 && idx >= h.stop_at);
+        const bool st = stop_set(stop) || (h.stop_at >= 0 && idx >= h.stop_at);
         if (st && stop_seen < 0) stop_seen = idx;
         return st;
     };
     for (int i = 0; i < ORBMI_GBA_MAX_ITERATIONS; i++) R->trials[i] = 0;
-    double lambda = 0, ni = 2, chi_initial = 0, chi_last = 0;
-    int nBad = 0;
+    S3oLm L{};
+    double chi_initial = 0, chi_last = 0;
     const bool empty = ne == 0;  // no active vertex: optimize() returns before its loop
     for (int i = 0; !empty && i < iterations && !terminate(); i++) {
         if ((rc = linearize()) || (rc = read_out())) return rc;
-        double currentChi = ho[kGbaOutChi];
-        const double iniChi = currentChi;
-        if (i == 0) {
-            lambda = 1e-5 * ho[kGbaOutMax];
-            ni = 2;
-            nBad = 0;
-            chi_initial = currentChi;
-        }
-        double rho = 0;
-        int qmax = 0;
+        if (i == 0) chi_initial = ho[kGbaOutChi];
+        lm_begin(L, i, ho[kGbaOutChi], [ho] { return 1e-5 * ho[kGbaOutMax]; });
+        bool more;
         do {
-            if ((rc = trial(lambda)) || (rc = read_out())) return rc;
+            if ((rc = trial(L.lambda)) || (rc = read_out())) return rc;
             const bool ok2 = ho[kGbaOutFail] == 0.0;
             if (!ok2) status |= ORBMI_GBA_SOLVE_FAILED;
             chi_last = ho[kGbaOutChi];
-            const double tempChi = ok2 ? chi_last : DBL_MAX;
-            rho = (currentChi - tempChi) / (ho[kGbaOutScale] + 1e-3);
-            if (rho > 0 && std::isfinite(tempChi)) {
-                double alpha = 1. - std::pow(2 * rho - 1, 3);
-                alpha = std::min(alpha, 2. / 3.);
-                lambda *= std::max(1. / 3., alpha);
-                ni = 2;
-                currentChi = tempChi;
-                cur ^= 1;
-            } else {
-                lambda *= ni;
-                ni *= 2;
-                status |= ORBMI_GBA_REJECTED;
-            }
-            qmax++;
-            R->trials[i] = qmax;
-        } while (rho < 0 && qmax < 10 && !terminate());
+            if (lm_trial(L, ok2, chi_last, ho[kGbaOutScale], &more, LmCubePow())) cur ^= 1;
+            else status |= ORBMI_GBA_REJECTED;
+            R->trials[i] = L.qmax;
+        } while (more && !terminate());
         it++;
-        if (qmax == 10 || rho == 0) { status |= ORBMI_GBA_TERMINATE; break; }
-        if ((iniChi - currentChi) * 1e3 < iniChi) nBad++;
-        else nBad = 0;
-        if (nBad >= 3) { status |= ORBMI_GBA_TERMINATE; break; }
+        if (lm_end(L)) { status |= ORBMI_GBA_TERMINATE; break; }
     }
     if (empty) status |= ORBMI_GBA_TERMINATE;
     hipLaunchKernelGGL(k_gba_finish, blocks(std::max(nkf, npt), kGbaThreads), dim3(kGbaThreads), 0, s, a, (const double*)Tb[cur],
-                       (const double*)Xb[cur], (float*)(B + o_otcw), (float*)(B + o_opos), B + o_oinc);
+                       (const double*)Xb[cur], o_tcw, o_pos, o_inc);
     ORBMI_HIP(hipGetLastError());
-    if (nkf) ORBMI_HIP(hipMemcpyAsync(R->tcw, B + o_otcw, 64 * (size_t)nkf, hipMemcpyDeviceToHost, s));
-    if (npt) ORBMI_HIP(hipMemcpyAsync(R->pos, B + o_opos, 12 * (size_t)npt, hipMemcpyDeviceToHost, s));
-    if (npt) ORBMI_HIP(hipMemcpyAsync(R->included, B + o_oinc, (size_t)npt, hipMemcpyDeviceToHost, s));
+    if (nkf) ORBMI_HIP(hipMemcpyAsync(R->tcw, o_tcw, 64 * nK, hipMemcpyDeviceToHost, s));
+    if (npt) ORBMI_HIP(hipMemcpyAsync(R->pos, o_pos, 12 * nP, hipMemcpyDeviceToHost, s));
+    if (npt) ORBMI_HIP(hipMemcpyAsync(R->included, o_inc, nP, hipMemcpyDeviceToHost, s));
     ORBMI_HIP(hipStreamSynchronize(s));
     R->iterations = it;
     R->chi2_initial = chi_initial;
@@ -770,6 +597,6 @@ extern "C" int orbmi_bundle_adjustment(orbmi_ba* b, const orbmi_ba_problem* P, i
     R->status = status;
     R->n_free = nf;
     R->n_blocks = nblk;
-    for (int k = 0; k < 4; k++) R->phase_ms[k] = ph.ms[k];
+    for (int k = 0; k < 4; k++) R->phase_ms[k] = phase_ms[k];
     return ORBMI_OK;
 }

@@ -29,6 +29,8 @@
 // ORB-SLAM "3 bad iterations" stop, stale edge errors after a rejected trial, push/pop of
 // the estimates (pointer swap of current / trial buffers), Huber kernels removed for the
 // second pass.  Every reduction has a fixed order (deterministic).  Parity with the oracle: 1e-4.
+// The host side of the entry is: argument checks, the plan (ba_graph.h: validation, index tables,
+// the block table and the check of all of them, shared with gba.hip), the arena, the launches.
 #include <algorithm>
 #include <cfloat>
 #include <chrono>
@@ -59,11 +61,11 @@
 #pragma clang fp contract(fast)
 
 #include "ba_edge.h"    // the edge arithmetic, under the contraction mode set above
-#include "ba_handle.h"  // struct orbmi_ba
+#include "ba_graph.h"   // the host plan (kBaMaxPoses: 6 * 30 = 180 unknowns)
+#include "ba_handle.h"  // struct orbmi_ba, stop_set, ArenaWalk
 
 namespace orbmi {
 
-constexpr int kBaMaxPoses = 30;                        // 6*30 = 180 unknowns
 constexpr int kBaMaxN = 6 * kBaMaxPoses;
 constexpr int kBaPacked = kBaMaxN * (kBaMaxN + 1) / 2;  // 16290 doubles = 127 KiB
 constexpr int kBaMaxKf = 1024;
@@ -1723,6 +1725,7 @@ __device__ inline double wave_sum_fixed(const double* p, int n) {
     return __shfl(s, 0, 64);
 }
 
+// (The Levenberg rule written out here is the one csrc/g2o_lm.h states.)
 // one wave, after each trial: OptimizationAlgorithmLevenberg::solve's decision
 // (levenberg.cpp:104-164) and SparseOptimizer::optimize's loop (sparse_optimizer.cpp:354-419)
 // with ORB-SLAM2's 3-bad-iterations stop; pbStopFlag is read through the host-mapped mirror.
@@ -1995,59 +1998,6 @@ struct BaTrace {
     }
 };
 
-// the caller's stop flag (bool* pbStopFlag, src/Optimizer.cc:483), written by other threads:
-// read with an atomic load
-inline bool stop_set(const volatile int* stop) { return stop && __atomic_load_n(stop, __ATOMIC_ACQUIRE) != 0; }
-
-// The pose-pair blocks' ids.  Pair l = (ra, rb >= ra) in row-major order (l = ra nf - ra (ra - 1)
-// / 2 + rb - ra) runs as block blk_id[l] of k_ba_schur.  Placed by row: the blocks of row ra
-// (which all read the Hpl blocks of keyframe ra's edges) go to ids of one residue mod 8 -- one XCD
-// under the round-robin dispatch, so their re-reads of those blocks hit one L2 (speed only).
-// Rows are dealt to the 8 residues largest first onto the least loaded; pairs beyond a residue's
-// ids take the ids left over, in increasing order.
-// Every block id in [0, nblk) must name exactly one pair: an id no pair took would leave its
-// blk_kf entry to whatever the pinned staging buffer last held, and the pair kernels index
-// pose_idx / kf_start with it (the round-4 r04x illegal address, from a work-in-progress form of
-// this table, on the first call that reused a larger graph's staging buffer).  So the table is
-// checked before it is used: false = not a permutation (never, by construction; tested for
-// every nf by tests/test_capi_exports.py through orbmi_debug_ba_schur_blocks).
-bool ba_block_table(int nf, std::vector<int>& blk_id) {
-    const int nblk = nf * (nf + 1) / 2;
-    blk_id.assign(std::max(nblk, 1), -1);
-    const int R = 8;
-    std::vector<int> load(R, 0), grp(std::max(nf, 1));
-    for (int r = 0; r < nf; r++) {  // row r holds nf - r pairs: already largest first
-        const int g = (int)(std::min_element(load.begin(), load.end()) - load.begin());
-        grp[r] = g;
-        load[g] += nf - r;
-    }
-    std::vector<int> next(R);
-    for (int g = 0; g < R; g++) next[g] = g;
-    std::vector<char> used(std::max(nblk, 1), 0);
-    std::vector<int> spill;
-    int l = 0;
-    for (int ra = 0; ra < nf; ra++)
-        for (int rb = ra; rb < nf; rb++, l++) {
-            const int g = grp[ra];
-            if (next[g] < nblk) { blk_id[l] = next[g]; used[next[g]] = 1; next[g] += R; }
-            else spill.push_back(l);
-        }
-    int free_id = 0;
-    for (int x : spill) {
-        while (free_id < nblk && used[free_id]) free_id++;
-        if (free_id >= nblk) return false;
-        blk_id[x] = free_id;
-        used[free_id] = 1;
-    }
-    std::vector<char> hit(std::max(nblk, 1), 0);
-    for (int x = 0; x < nblk; x++) {
-        const int id = blk_id[x];
-        if (id < 0 || id >= nblk || hit[id]) return false;
-        hit[id] = 1;
-    }
-    return true;
-}
-
 // Trial steps enqueued beyond the iterations still to run: a rejected trial consumes one step
 // without finishing an iteration, so the steps enqueued up front usually finish optimize().
 constexpr int kBaStepSlack = 1;
@@ -2238,50 +2188,35 @@ int orbmi_local_bundle_adjustment(orbmi_ba* b, const orbmi_ba_problem* P, orbmi_
     }
     const int nkf = P->nkf, npt = P->npt, ne = P->nedge;
     if (nkf > kBaMaxKf) return ORBMI_E_UNSUPPORTED;
-    // host-side graph indexing: edges grouped by point (the reference inserts them point by
-    // point), CSR by keyframe, keyframes ordered by id (SparseOptimizer vertex order).  The index
-    // arrays are written straight into the pinned staging buffer that goes up in one copy.
-    {
-        // one edge per (point, keyframe), as the reference builds the graph from a map point's
-        // observations (a std::map per point): the per-keyframe Schur blocks sum each edge's
-        // B D^-1 B^T with itself only, so a second edge of one pair would lose its cross terms
-        std::vector<int> last_pt(std::max(nkf, 1), -1);
-        for (int i = 0; i < ne; i++) {
-            const orbmi_ba_edge& e = P->edges[i];
-            if (e.point < 0 || e.point >= npt || e.kf < 0 || e.kf >= nkf) return ORBMI_E_ARG;
-            if (i && e.point < P->edges[i - 1].point) return ORBMI_E_ARG;
-            if (last_pt[e.kf] == e.point) return ORBMI_E_ARG;  // (edges come grouped by point)
-            last_pt[e.kf] = e.point;
-        }
-    }
-    std::vector<int> order(std::max(nkf, 1));
-    for (int k = 0; k < nkf; k++) order[k] = k;
-    std::stable_sort(order.begin(), order.begin() + nkf, [&](int x, int y) { return P->kfs[x].id < P->kfs[y].id; });
-    // Schur pair lists: blocks = pairs of non-fixed keyframes (a, b) with rank(a) <= rank(b)
-    // in id order; pairs (e_a, e_b) = two observations of one point (both orders inside a
-    // keyframe).  Pose indices follow the same order, so block (a, b) is (i <= j).
-    std::vector<int> rank(std::max(nkf, 1), -1), free_kf;
-    for (int oi = 0; oi < nkf; oi++)
-        if (!P->kfs[order[oi]].fixed) { rank[order[oi]] = (int)free_kf.size(); free_kf.push_back(order[oi]); }
-    const int nf = (int)free_kf.size();
+    // ---- the plan (ba_graph.h): edges grouped by point (the reference inserts them point by
+    // point), CSR by keyframe, keyframes ordered by id (SparseOptimizer vertex order); every
+    // non-fixed keyframe is a pose block.  Schur blocks = pairs of non-fixed keyframes (a, b) with
+    // rank(a) <= rank(b) in id order, so block (a, b) is (i <= j); their pair lists (e_a, e_b) =
+    // two observations of one point (both orders inside a keyframe) are built on the device.
+    std::vector<int> order(std::max(nkf, 1)), rank(std::max(nkf, 1)), free_kf(std::max(nkf, 1));
+    const int nf = ba_graph_rank(*P, nullptr, order.data(), rank.data(), free_kf.data());
     const long long nblk_ll = (long long)nf * (nf + 1) / 2;
     if (nblk_ll > (1 << 20)) return ORBMI_E_UNSUPPORTED;
     const int nblk = (int)nblk_ll;
     std::vector<int> blk_id;
     if (!ba_block_table(nf, blk_id)) return ORBMI_E_UNSUPPORTED;
-    auto blk_of = [nf, &blk_id](int ra, int rb) { return blk_id[ra * nf - ra * (ra - 1) / 2 + (rb - ra)]; };
-    // ---- one device arena; the graph and its index arrays go up in one copy
+    // ---- one device arena, every slot listed once (ArenaWalk).  The graph and its index arrays
+    // come first and contiguous: they are written straight into the pinned staging buffer, laid out
+    // the same, and go up in one copy.
     const int nb_e = std::max(1, (ne + kBaBlock - 1) / kBaBlock), nb_p = std::max(1, (npt + kBaBlock - 1) / kBaBlock);
     const int nb_q = std::max(1, (npt + kBaUpdPts - 1) / kBaUpdPts);
-    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off += al(std::max(bytes, (size_t)8)); return o; };
-    // uploaded region first (contiguous)
-    const size_t o_kfs = take(sizeof(orbmi_ba_keyframe) * nkf), o_pts = take(sizeof(orbmi_ba_point) * npt),
-                 o_edges = take(sizeof(orbmi_ba_edge) * ne), o_order = take(4 * nkf), o_pts_start = take(4 * (npt + 1)),
-                 o_kfs_start = take(4 * (nkf + 1)), o_kf_edges = take(4 * (size_t)ne), o_kf_pos = take(4 * (size_t)ne),
-                 o_kf_pt = take(4 * (size_t)ne), o_blk_kf = take(8 * (size_t)nblk), o_free = take(4 * (size_t)nf);
-    const size_t up_bytes = off;
+    const size_t nE = (size_t)ne, nP = (size_t)npt, nK = (size_t)nkf;
+    struct Upload {
+        orbmi_ba_keyframe* kfs; orbmi_ba_point* pts; orbmi_ba_edge* edges;
+        int *order, *pt_start, *kf_start, *kf_edges, *kf_pos, *kf_pt, *blk_kf, *free_kf;
+    } hs{}, ds{};
+    auto upload = [&](ArenaWalk& A, Upload& u) {
+        A(u.kfs, nK); A(u.pts, nP); A(u.edges, nE); A(u.order, nK); A(u.pt_start, nP + 1); A(u.kf_start, nK + 1);
+        A(u.kf_edges, nE); A(u.kf_pos, nE); A(u.kf_pt, nE); A(u.blk_kf, 2 * (size_t)nblk); A(u.free_kf, (size_t)nf);
+    };
+    ArenaWalk size;
+    upload(size, hs);
+    const size_t up_bytes = size.off;
     hipStream_t s = h.stream;
     // the previous call's upload may still be reading the staging buffer (only that copy is
     // waited for: the stream's other work, e.g. the searches enqueued before this call on a
@@ -2294,74 +2229,56 @@ int orbmi_local_bundle_adjustment(orbmi_ba* b, const orbmi_ba_problem* P, orbmi_
         ORBMI_HIP(hipHostMalloc((void**)&h.h_stage, up_bytes));
         h.cap_stage = up_bytes;
     }
-    uint8_t* S = h.h_stage;
-    int* pt_start = (int*)(S + o_pts_start);
-    int* kf_start = (int*)(S + o_kfs_start);
-    int* kf_edges = (int*)(S + o_kf_edges);
-    int* kf_pos = (int*)(S + o_kf_pos);
-    int* kf_pt = (int*)(S + o_kf_pt);
-    std::memset(pt_start, 0, 4 * (size_t)(npt + 1));
-    std::memset(kf_start, 0, 4 * (size_t)(nkf + 1));
-    for (int i = 0; i < ne; i++) { pt_start[P->edges[i].point + 1]++; kf_start[P->edges[i].kf + 1]++; }
-    for (int p = 0; p < npt; p++) pt_start[p + 1] += pt_start[p];
-    for (int k = 0; k < nkf; k++) kf_start[k + 1] += kf_start[k];
-    // capacity of the pair lists (built on the device): sum over points of (free edges)^2
-    long long npair_cap = 0;
-    {
-        std::vector<int> fill(kf_start, kf_start + nkf);
-        int p = -1;
-        long long m = 0;
-        for (int i = 0; i < ne; i++) {
-            const orbmi_ba_edge& e = P->edges[i];
-            const int j = fill[e.kf]++;
-            kf_pos[i] = j;
-            kf_edges[j] = i;
-            kf_pt[j] = e.point;
-            if (e.point != p) { npair_cap += m * m; m = 0; p = e.point; }
-            m += rank[e.kf] >= 0;
-        }
-        npair_cap += m * m;
-    }
+    ArenaWalk stage{h.h_stage};
+    upload(stage, hs);
+    long long npair_cap = 0;  // capacity of the pair lists (built on the device)
+    int rc = ba_graph_index(*P, hs.pt_start, hs.kf_start, hs.kf_edges, hs.kf_pos, hs.kf_pt, rank.data(), &npair_cap);
+    if (rc) return rc;  // ORBMI_E_ARG: the edges' validation, in the counting pass
     if (npair_cap > (1LL << 28)) return ORBMI_E_UNSUPPORTED;
-    const int npair = (int)npair_cap;
-    if (nkf) std::memcpy(S + o_order, order.data(), 4 * (size_t)nkf);
-    if (nf) std::memcpy(S + o_free, free_kf.data(), 4 * (size_t)nf);
-    {
-        int* bk = (int*)(S + o_blk_kf);
-        for (int ra = 0; ra < nf; ra++)
-            for (int rb = ra; rb < nf; rb++) { bk[2 * blk_of(ra, rb)] = free_kf[ra]; bk[2 * blk_of(ra, rb) + 1] = free_kf[rb]; }
-    }
-    auto put = [&](size_t o, const void* src, size_t bytes) { if (bytes) std::memcpy(S + o, src, bytes); };
-    put(o_kfs, P->kfs, sizeof(orbmi_ba_keyframe) * nkf);
-    put(o_pts, P->pts, sizeof(orbmi_ba_point) * npt);
-    put(o_edges, P->edges, sizeof(orbmi_ba_edge) * ne);
-    const size_t o_blk_cnt = take(4 * (size_t)nblk), o_blk_start = take(4 * ((size_t)nblk + 1)),
-                 o_pairs = take(8 * (size_t)npair), o_pairpt = take(4 * (size_t)npair);
-    const size_t o_e_pi = take(4 * (size_t)ne), o_T0 = take(64 * nkf), o_T1 = take(64 * nkf), o_X0 = take(32 * npt),
-                 o_X1 = take(32 * npt), o_err = take(24 * (size_t)ne), o_eflag = take(ne), o_pidx = take(4 * nkf), o_kfact = take(4 * nkf),
-                 o_pkf = take(4 * kBaMaxPoses), o_Hpl = take(2 * 144 * (size_t)ne), o_Hle = take(2 * 72 * (size_t)ne),
-                 o_Hpe = take(2 * 216 * (size_t)ne), o_Hll = take(2 * 72 * npt), o_bl = take(2 * 24 * npt),
-                 o_Hpp = take(288 * kBaMaxPoses), o_bp = take(48 * kBaMaxPoses), o_S = take(8 * (size_t)kBaPacked),
-                 o_bs = take(8 * kBaMaxN), o_xp = take(8 * kBaMaxN), o_scal = take(64), o_plin = take(8 * (size_t)nb_e),
-                 o_ptchi = take(8 * (size_t)nb_q), o_ptsc = take(8 * (size_t)nb_q),
-                 o_pmax = take(8 * ((size_t)nb_p + kBaMaxPoses)), o_istat = take(32), o_ctl = take(sizeof(BaCtl)),
-                 o_otcw = take(64 * nkf), o_opos = take(12 * npt), o_oerase = take(ne),
-                 o_pkfs = take(8 * 64 * kSchurKfSplit * (size_t)kBaMaxPoses), o_arrkf = take(4 * kBaMaxPoses);
-    if (off > h.cap) {
+    const size_t npair = (size_t)npair_cap;
+    auto put = [](void* dst, const void* src, size_t bytes) { if (bytes) std::memcpy(dst, src, bytes); };
+    put(hs.order, order.data(), 4 * nK);
+    put(hs.free_kf, free_kf.data(), 4 * (size_t)nf);
+    ba_block_kf(nf, blk_id, free_kf.data(), hs.blk_kf);
+    // (never, by construction; the per-edge part of the check ran inside the fill)
+    if (!ba_tables_ok(*P, nf, hs.pt_start, hs.kf_start, hs.kf_edges, hs.kf_pos, hs.kf_pt, rank.data(), hs.free_kf, hs.blk_kf, false))
+        return ORBMI_E_UNSUPPORTED;
+    put(hs.kfs, P->kfs, sizeof(orbmi_ba_keyframe) * nK);
+    put(hs.pts, P->pts, sizeof(orbmi_ba_point) * nP);
+    put(hs.edges, P->edges, sizeof(orbmi_ba_edge) * nE);
+    BaDev a;
+    float *o_tcw, *o_pos;  // the outputs: contiguous (tcw, pos, erase) for the single read-back
+    unsigned char* out_erase;
+    auto work = [&](ArenaWalk& A) {
+        A(a.blk_cnt, (size_t)nblk); A(a.blk_start, (size_t)nblk + 1); A(a.blk_pairs, npair); A(a.blk_pt, npair);
+        A(a.e_pi, nE); A(a.Tb[0], 8 * nK); A(a.Tb[1], 8 * nK); A(a.Xb[0], 4 * nP); A(a.Xb[1], 4 * nP); A(a.err, 3 * nE);
+        A(a.eflag, nE); A(a.pose_idx, nK); A(a.kf_act, nK); A(a.pose_kf, kBaMaxPoses);
+        // two linear-system buffers each (ctl.lin selects the current one)
+        A(a.Hplb[0], 2 * 18 * nE); A(a.Hleb[0], 2 * 9 * nE); A(a.Hpeb[0], 2 * 27 * nE); A(a.Hllb[0], 2 * 9 * nP);
+        A(a.blb[0], 2 * 3 * nP); A(a.Hpp, 36 * kBaMaxPoses); A(a.bp, 6 * kBaMaxPoses); A(a.S, kBaPacked); A(a.bs, kBaMaxN);
+        A(a.xp, kBaMaxN); A(a.scal, 8); A(a.part_lin, nb_e); A(a.part_tchi, nb_q); A(a.part_tscale, nb_q);
+        A(a.part_max, (size_t)nb_p + kBaMaxPoses); A(a.istat, 8); A(a.ctl, 1); A(o_tcw, 16 * nK); A(o_pos, 3 * nP);
+        A(out_erase, nE); A(a.part_kf, (size_t)64 * kSchurKfSplit * kBaMaxPoses); A(a.arrive_kf, kBaMaxPoses);
+    };
+    work(size);
+    if (size.off > h.cap) {
         if (h.d_buf) (void)hipFree(h.d_buf);
         h.d_buf = nullptr;
         h.cap = 0;
-        ORBMI_HIP(hipMalloc((void**)&h.d_buf, off));
-        h.cap = off;
+        ORBMI_HIP(hipMalloc((void**)&h.d_buf, size.off));
+        h.cap = size.off;
     }
-    uint8_t* B = h.d_buf;
+    ArenaWalk bind{h.d_buf};
+    upload(bind, ds);
+    work(bind);
     tr.mark("host_index");
     // (the arena's previous reader, the last call's solve, finished before that call returned)
     if (!h.up_stream) ORBMI_HIP(orbmi::stream_create(&h.up_stream, "BA"));
-    ORBMI_HIP(hipMemcpyAsync(B, S, up_bytes, hipMemcpyHostToDevice, h.up_stream));
+    ORBMI_HIP(hipMemcpyAsync(h.d_buf, h.h_stage, up_bytes, hipMemcpyHostToDevice, h.up_stream));
     ORBMI_HIP(hipEventRecord(h.up_done, h.up_stream));
     ORBMI_HIP(hipStreamWaitEvent(s, h.up_done, 0));
-    const size_t out_bytes = o_oerase + (size_t)std::max(ne, 1) - o_otcw;  // tcw, pos, erase (aligned)
+    const size_t off_pos = (size_t)((uint8_t*)o_pos - (uint8_t*)o_tcw), off_erase = (size_t)(out_erase - (uint8_t*)o_tcw);
+    const size_t out_bytes = off_erase + (size_t)std::max(ne, 1);  // tcw, pos, erase (aligned)
     if (out_bytes > h.cap_out) {
         if (h.h_out) (void)hipHostFree(h.h_out);
         h.h_out = nullptr;
@@ -2370,55 +2287,23 @@ int orbmi_local_bundle_adjustment(orbmi_ba* b, const orbmi_ba_problem* P, orbmi_
         h.cap_out = out_bytes;
     }
     uint8_t* const Ho = h.h_out;
-    BaDev a;
     a.nkf = nkf; a.npt = npt; a.nedge = ne; a.nblk = nblk; a.nf = nf;
     a.nb_e = nb_e; a.nb_p = nb_p; a.nb_q = nb_q;
-    a.ctl = (BaCtl*)(B + o_ctl);
     a.stop = stop ? h.d_stop : nullptr;
     a.stop_at = h.stop_at;
     // the mirror starts with the flag's value now; Runner::wait keeps it current (the device reads
     // it only at the checks)
     *(volatile int*)h.h_stop = stop_set(stop) ? 1 : 0;
-    a.Tb[0] = (double*)(B + o_T0); a.Tb[1] = (double*)(B + o_T1);
-    a.Xb[0] = (double*)(B + o_X0); a.Xb[1] = (double*)(B + o_X1);
-    a.part_lin = (double*)(B + o_plin); a.part_tchi = (double*)(B + o_ptchi); a.part_tscale = (double*)(B + o_ptsc);
-    a.part_max = (double*)(B + o_pmax);
-    a.kfs = (const orbmi_ba_keyframe*)(B + o_kfs);
-    a.pts = (const orbmi_ba_point*)(B + o_pts);
-    a.edges = (const orbmi_ba_edge*)(B + o_edges);
-    a.kf_order = (const int*)(B + o_order);
-    a.free_kf = (const int*)(B + o_free);
-    a.part_kf = (double*)(B + o_pkfs);
-    a.arrive_kf = (unsigned*)(B + o_arrkf);
-    a.pt_start = (const int*)(B + o_pts_start);
-    a.kf_start = (const int*)(B + o_kfs_start);
-    a.kf_edges = (const int*)(B + o_kf_edges);
-    a.kf_pos = (const int*)(B + o_kf_pos);
-    a.kf_pt = (const int*)(B + o_kf_pt);
-    a.e_pi = (int*)(B + o_e_pi);
-    a.blk_kf = (const int*)(B + o_blk_kf);
-    a.blk_cnt = (int*)(B + o_blk_cnt);
-    a.blk_start = (int*)(B + o_blk_start);
-    a.blk_pairs = (int2*)(B + o_pairs);
-    a.blk_pt = (int*)(B + o_pairpt);
-    a.err = (double*)(B + o_err); a.eflag = B + o_eflag;
-    a.pose_idx = (int*)(B + o_pidx); a.pose_kf = (int*)(B + o_pkf); a.kf_act = (int*)(B + o_kfact);
-    for (int L = 0; L < 2; L++) {  // two linear-system buffers (ctl.lin selects the current one)
-        a.Hplb[L] = (double*)(B + o_Hpl) + (size_t)L * 18 * ne;
-        a.Hleb[L] = (double*)(B + o_Hle) + (size_t)L * 9 * ne;
-        a.Hpeb[L] = (double*)(B + o_Hpe) + (size_t)L * 27 * ne;
-        a.Hllb[L] = (double*)(B + o_Hll) + (size_t)L * 9 * npt;
-        a.blb[L] = (double*)(B + o_bl) + (size_t)L * 3 * npt;
-    }
+    a.kfs = ds.kfs; a.pts = ds.pts; a.edges = ds.edges; a.kf_order = ds.order; a.free_kf = ds.free_kf;
+    a.pt_start = ds.pt_start; a.kf_start = ds.kf_start; a.kf_edges = ds.kf_edges; a.kf_pos = ds.kf_pos;
+    a.kf_pt = ds.kf_pt; a.blk_kf = ds.blk_kf;
+    a.Hplb[1] = a.Hplb[0] + 18 * nE; a.Hleb[1] = a.Hleb[0] + 9 * nE; a.Hpeb[1] = a.Hpeb[0] + 27 * nE;
+    a.Hllb[1] = a.Hllb[0] + 9 * nP; a.blb[1] = a.blb[0] + 3 * nP;
     a.Hpl = a.Hplb[0]; a.Hle = a.Hleb[0]; a.Hpe = a.Hpeb[0]; a.Hll = a.Hllb[0]; a.bl = a.blb[0];
-    a.Hpp = (double*)(B + o_Hpp); a.bp = (double*)(B + o_bp);
-    a.S = (double*)(B + o_S); a.bs = (double*)(B + o_bs); a.xp = (double*)(B + o_xp);
-    a.scal = (double*)(B + o_scal); a.istat = (int*)(B + o_istat);
     // the one solver decision: k_ba_solve_mfma<mfma_T> up to kBaSolveMfmaMaxPoses free keyframes
     // (6 nf unknowns padded to mfma_T tiles of 16), k_ba_solve beyond (Runner::step launches it)
     a.mfma_T = nf <= kBaSolveMfmaMaxPoses ? std::max(1, (6 * nf + 15) / 16) : 0;
     Runner r{h, a, stop};
-    unsigned char* out_erase = B + o_oerase;
     const int nb_all = std::max(1, (std::max(std::max(nkf, npt), ne) + kBaBlock - 1) / kBaBlock);
     hipLaunchKernelGGL(k_ba_setup, dim3(nb_all), dim3(kBaBlock), 0, s, a, a.Tb[0], a.Xb[0], out_erase);
     if (nblk > 0) {
@@ -2440,14 +2325,13 @@ int orbmi_local_bundle_adjustment(orbmi_ba* b, const orbmi_ba_problem* P, orbmi_
         }
         for (int k = 0; k < (from <= 1 ? 10 + slack : more); k++) r.step(2);
         r.epilogue(2);
-        hipLaunchKernelGGL(k_ba_finish, dim3(nb_all), dim3(kBaBlock), 0, s, a, (float*)(B + o_otcw), (float*)(B + o_opos),
-                           out_erase);
+        hipLaunchKernelGGL(k_ba_finish, dim3(nb_all), dim3(kBaBlock), 0, s, a, o_tcw, o_pos, out_erase);
         hipError_t e = hipSuccess;
         // the outputs are contiguous in the arena (tcw, pos, erase): one copy into pinned memory
-        if (e == hipSuccess) e = hipMemcpyAsync(Ho, B + o_otcw, o_oerase + ne - o_otcw, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(Ho, o_tcw, off_erase + nE, hipMemcpyDeviceToHost, s);
         return e;
     };
-    int rc, from = 0, more = 0;
+    int from = 0, more = 0;
     for (;;) {
         ORBMI_HIP(enqueue(from, more));
         ORBMI_HIP(hipGetLastError());
@@ -2463,8 +2347,8 @@ int orbmi_local_bundle_adjustment(orbmi_ba* b, const orbmi_ba_problem* P, orbmi_
     }
     tr.mark("optimize+finish");
     if (nkf) std::memcpy(R->tcw, Ho, 64 * (size_t)nkf);
-    if (npt) std::memcpy(R->pos, Ho + (o_opos - o_otcw), 12 * (size_t)npt);
-    if (ne) std::memcpy(R->erase, Ho + (o_oerase - o_otcw), (size_t)ne);
+    if (npt) std::memcpy(R->pos, Ho + off_pos, 12 * (size_t)npt);
+    if (ne) std::memcpy(R->erase, Ho + off_erase, (size_t)ne);
     const BaCtl& c = *h.h_ctl;
     const bool second = c.do_more != 0;
     R->iterations[0] = c.it_out[0];

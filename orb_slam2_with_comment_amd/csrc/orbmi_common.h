@@ -61,6 +61,29 @@ inline bool on_device(const void* p) {
     return at.type == hipMemoryTypeDevice || at.type == hipMemoryTypeManaged;
 }
 
+// HIP events around one phase of a profiled call (host only): end() waits for the phase and adds
+// its device time in milliseconds to *acc.  Off, both do nothing.
+struct PhaseTimer {
+    hipStream_t s;
+    bool on;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    PhaseTimer(hipStream_t stream, bool on_) : s(stream), on(on_) {
+        if (on && (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess)) on = false;
+    }
+    ~PhaseTimer() {
+        if (e0) (void)hipEventDestroy(e0);
+        if (e1) (void)hipEventDestroy(e1);
+    }
+    void begin() { if (on) (void)hipEventRecord(e0, s); }
+    template <class T>
+    void end(T* acc) {
+        float ms = 0;
+        if (on && hipEventRecord(e1, s) == hipSuccess && hipEventSynchronize(e1) == hipSuccess &&
+            hipEventElapsedTime(&ms, e0, e1) == hipSuccess)
+            *acc += ms;
+    }
+};
+
 // Non-blocking stream of one handle. ORBMI_PRIO_<ROLE>=high|low (ROLE = MATCHER, POSE, BA,
 // VOCAB, EXTRACTOR) selects the device's greatest / least stream priority, else the default.
 inline hipError_t stream_create(hipStream_t* s, const char* role) {

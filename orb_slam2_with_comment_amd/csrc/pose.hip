@@ -558,6 +558,7 @@ __global__ __launch_bounds__(kPoseThreads) void k_pose_opt(orbmi_pose_frame* __r
             nact = pose_reduce1(nact, red1[rb]);
             rb ^= 1;
             if (nact > 0) {
+                // (The Levenberg rule written out below is the one csrc/g2o_lm.h states.)
                 // ---- optimize(10) on the level-0 edges.  Every wave runs the edge passes and the
                 // Levenberg decisions (replicated: the same instructions on the same LDS values, so
                 // every wave takes the same branch).  Wave 0 holds the reduced system and publishes,

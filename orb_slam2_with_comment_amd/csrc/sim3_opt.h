@@ -8,6 +8,8 @@
 //   BaseBinaryEdge::constructQuadraticForm         core/base_binary_edge.hpp:91-113
 //   RobustKernelHuber::robustify                   core/robust_kernel_impl.cpp:78-91
 //   OptimizationAlgorithmLevenberg::solve          core/optimization_algorithm_levenberg.cpp:61-189
+//                                                  (the decision itself: g2o_lm.h, shared with the
+//                                                  essential graph and global BA)
 // All fp64, one rounding per operation in the order written (-ffp-contract=off).  sin, cos and exp
 // come from the platform (csrc/trig_f64.h on the device), so host and device agree to rounding,
 // not bit for bit; the perturbations of the numeric Jacobians take the small-angle branch, which
@@ -25,12 +27,8 @@
 #include <math.h>
 #include <stdint.h>
 
-#ifndef __host__
-#define __host__
-#endif
-#ifndef __device__
-#define __device__
-#endif
+#include "g2o_lm.h"
+
 #if defined(__HIP_DEVICE_COMPILE__)
 #include "trig_f64.h"
 #endif
@@ -41,7 +39,6 @@ namespace orbmi {
 
 constexpr double kS3oDelta = 1e-9;  // BaseBinaryEdge::linearizeOplus
 constexpr int kS3oAcc = 36;         // 28 upper entries of H, 7 of b, the robust chi2
-constexpr int kS3oMaxTrials = 10;   // _maxTrialsAfterFailure
 
 struct Sim3d {
     double q[4];  // x y z w (Eigen's coefficient order)
@@ -383,18 +380,11 @@ S3O_FN bool s3o_solve7(const double* H, const double* b, double lam, double* x) 
     return ok;
 }
 
-// The Levenberg state of one optimize() and the decision after one trial
-// (optimization_algorithm_levenberg.cpp:99-163)
-struct S3oLm {
-    double lambda, ni, currentChi, iniChi, rho;
-    int qmax, nBad;
-};
-
+// The Levenberg decision is g2o_lm.h's; OptimizeSim3 brings computeLambdaInit over its 7 diagonal
+// entries and computeScale's seven terms.
 // After buildSystem of iteration `it`: H = the 28 upper entries
 S3O_FN void s3o_lm_begin(S3oLm& L, int it, const double* H, double chi) {
-    L.currentChi = chi;
-    L.iniChi = chi;
-    if (it == 0) {
+    lm_begin(L, it, chi, [H] {
         double m = 0;
         int q = 0;
 #pragma unroll
@@ -403,45 +393,16 @@ S3O_FN void s3o_lm_begin(S3oLm& L, int it, const double* H, double chi) {
             m = a > m ? a : m;  // std::max(fabs(h), m): a NaN diagonal is passed over
             q += 7 - r;
         }
-        L.lambda = 1e-5 * m;
-        L.ni = 2;
-        L.nBad = 0;
-    }
-    L.rho = 0;
-    L.qmax = 0;
+        return 1e-5 * m;
+    });
 }
 
 // One trial's verdict: true = the step is kept.  *more = the do-while goes on.
 S3O_FN bool s3o_lm_trial(S3oLm& L, bool ok2, double tempChi, const double* x, const double* b, bool* more) {
-    if (!ok2) tempChi = 1.7976931348623157e308;
     double scale = 0;
 #pragma unroll
     for (int j = 0; j < 7; j++) scale = scale + x[j] * (L.lambda * x[j] + b[j]);
-    scale = scale + 1e-3;
-    L.rho = (L.currentChi - tempChi) / scale;
-    const bool accept = L.rho > 0 && tempChi - tempChi == 0;  // isfinite
-    if (accept) {
-        const double z = 2 * L.rho - 1;
-        double alpha = 1. - z * z * z;
-        alpha = alpha < 2. / 3. ? alpha : 2. / 3.;
-        L.lambda = L.lambda * (1. / 3. > alpha ? 1. / 3. : alpha);
-        L.ni = 2;
-        L.currentChi = tempChi;
-    } else {
-        L.lambda = L.lambda * L.ni;
-        L.ni = L.ni * 2;
-    }
-    L.qmax++;
-    *more = L.rho < 0 && L.qmax < kS3oMaxTrials;
-    return accept;
-}
-
-// After the do-while: true = optimize() stops (Terminate)
-S3O_FN bool s3o_lm_end(S3oLm& L) {
-    if (L.qmax == kS3oMaxTrials || L.rho == 0) return true;
-    if ((L.iniChi - L.currentChi) * 1e3 < L.iniChi) L.nBad++;
-    else L.nBad = 0;
-    return L.nBad >= 3;
+    return lm_trial(L, ok2, tempChi, scale, more, LmCubeMul());
 }
 
 // Converter::toCvMat(g2o::Sim3): (float)(s * R) and (float)t
@@ -512,7 +473,7 @@ struct S3oHost {
                 if (s3o_lm_trial(L, ok2, tempChi, x, acc + 28, &more)) S = T;
             } while (more);
             done++;
-            if (s3o_lm_end(L)) break;
+            if (lm_end(L)) break;
         }
         return done;
     }

@@ -186,7 +186,7 @@ __global__ __launch_bounds__(kS3oThreads) void k_sim3_opt(const Sim3OptDev* __re
             } while (more);
             if (tid == 0) {
                 if (phase == 0) its0++; else its1++;
-                sh.stop = s3o_lm_end(sh.L);
+                sh.stop = lm_end(sh.L);
             }
             __syncthreads();
             if (sh.stop) break;

@@ -208,4 +208,30 @@ __device__ inline double readlane_d(double v, int l) {
     return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
 }
 
+// One value per thread over a workgroup of NT, for the kernels whose sums must not depend on the
+// launch: thread t's partial goes into LDS (red: NT doubles), then a halving tree in a fixed order.
+// Every thread of the workgroup calls it and ends with the result.  (The headline kernels' block
+// sums -- lba.hip's block_sum, pose.hip's pose_reduce -- are other algorithms.)
+template <int NT, class Op>
+__device__ __forceinline__ double block_reduce_fixed(double part, double* red, Op op) {
+    red[threadIdx.x] = part;
+    __syncthreads();
+    for (int s = NT / 2; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s) red[threadIdx.x] = op(red[threadIdx.x], red[threadIdx.x + s]);
+        __syncthreads();
+    }
+    return red[0];
+}
+template <int NT>
+__device__ __forceinline__ double block_sum_fixed(double part, double* red) {
+    return block_reduce_fixed<NT>(part, red, [](double a, double b) { return a + b; });
+}
+// The sum of n values `stride` apart: thread t adds t, t + NT, ... in that order, then the tree
+template <int NT, class Index>
+__device__ __forceinline__ double strided_sum_fixed(const double* src, Index n, int stride, double* red) {
+    double part = 0;
+    for (Index i = threadIdx.x; i < n; i += NT) part = part + src[(size_t)i * stride];
+    return block_sum_fixed<NT>(part, red);
+}
+
 }  // namespace orbmi

@@ -81,6 +81,50 @@ class GlobalBA(LocalBA):
                 "status": r.status, "n_free": r.n_free, "n_blocks": r.n_blocks, "phase_ms": tuple(r.phase_ms)}
 
 
+def _ba_keyframes(kfs, fixed):
+    """BA_KF_DTYPE records of keyframes; fixed(i, keyframe) -> bool."""
+    K = np.zeros(len(kfs), BA_KF_DTYPE)
+    for i, k in enumerate(kfs):
+        K[i]["tcw"] = np.asarray(k.tcw, np.float32).reshape(-1)
+        K[i]["id"] = k.id
+        K[i]["fixed"] = 1 if fixed(i, k) else 0
+        K[i]["fx"], K[i]["fy"], K[i]["cx"], K[i]["cy"], K[i]["bf"] = k.cam.fx, k.cam.fy, k.cam.cx, k.cam.cy, k.cam.bf
+    return K
+
+
+def _ba_points_edges(mps, kfs):
+    """BA_PT_DTYPE records of points and the BA_EDGE_DTYPE rows of their observations: per point in
+    ascending keyframe id, bad keyframes and keyframes outside `kfs` skipped."""
+    kidx = {id(k): i for i, k in enumerate(kfs)}
+    P = np.zeros(len(mps), BA_PT_DTYPE)
+    if mps:
+        P["pos"] = np.array([mp.pos for mp in mps], np.float32).reshape(-1, 3)
+        P["id"] = [mp.id for mp in mps]
+        P["bad"] = [int(mp.bad) for mp in mps]
+    e_pt, e_kf, e_kp = [], [], []
+    for pi, mp in enumerate(mps):
+        for kf in sorted(mp.observations, key=lambda k: k.id):
+            ki = kidx.get(id(kf))
+            if kf.bad or ki is None:
+                continue
+            e_pt.append(pi)
+            e_kf.append(ki)
+            e_kp.append(mp.observations[kf])
+    E = np.zeros(len(e_pt), BA_EDGE_DTYPE)
+    if e_pt:
+        E["point"], E["kf"] = e_pt, e_kf
+        e_kf, e_kp = np.asarray(e_kf), np.asarray(e_kp)
+        for ki in np.unique(e_kf):   # one gather per keyframe
+            sel = e_kf == ki
+            k, j = kfs[ki], e_kp[sel]
+            kp = k.keys_un[j]
+            E["u"][sel] = kp["x"]
+            E["v"][sel] = kp["y"]
+            E["ur"][sel] = np.asarray(k.u_right, np.float32)[j]
+            E[E.dtype.names[5]][sel] = np.asarray(k.inv_level_sigma2, np.float32)[kp["octave"]]
+    return P, E
+
+
 def gather_global_ba(keyframes, map_points):
     """The graph of Optimizer::BundleAdjustment (src/Optimizer.cc:78-200) over the minimal map
     model: every keyframe and point that is not bad, one edge per observation in ascending keyframe
@@ -89,28 +133,8 @@ def gather_global_ba(keyframes, map_points):
     arrays and comes back with included = 0.  -> (BAProblem, keyframes kept, points kept)."""
     kfs = [k for k in keyframes if not k.bad]
     mps = [mp for mp in map_points if not mp.bad]
-    kidx = {id(k): i for i, k in enumerate(kfs)}
-    K = np.zeros(len(kfs), BA_KF_DTYPE)
-    for i, k in enumerate(kfs):
-        K[i]["tcw"] = np.asarray(k.tcw, np.float32).reshape(-1)
-        K[i]["id"] = k.id
-        K[i]["fixed"] = 1 if k.id == 0 else 0
-        K[i]["fx"], K[i]["fy"], K[i]["cx"], K[i]["cy"], K[i]["bf"] = k.cam.fx, k.cam.fy, k.cam.cx, k.cam.cy, k.cam.bf
-    P = np.zeros(len(mps), BA_PT_DTYPE)
-    if mps:
-        P["pos"] = np.array([mp.pos for mp in mps], np.float32).reshape(-1, 3)
-        P["id"] = [mp.id for mp in mps]
-    rows = []
-    for pi, mp in enumerate(mps):
-        for kf in sorted(mp.observations, key=lambda k: k.id):
-            ki = kidx.get(id(kf))
-            if kf.bad or ki is None:
-                continue
-            j = mp.observations[kf]
-            kp = kf.keys_un[j]
-            rows.append((pi, ki, kp["x"], kp["y"], np.float32(kf.u_right[j]),
-                         np.float32(kf.inv_level_sigma2[int(kp["octave"])])))
-    E = np.array(rows, BA_EDGE_DTYPE) if rows else np.zeros(0, BA_EDGE_DTYPE)
+    K = _ba_keyframes(kfs, lambda i, k: k.id == 0)
+    P, E = _ba_points_edges(mps, kfs)
     return BAProblem(K, P, E), kfs, mps
 
 
@@ -228,39 +252,8 @@ def gather_local_ba(pKF: KeyFrame):
                 if not kf.bad:
                     fixed.append(kf)
     kfs = local_kfs + fixed
-    kidx = {id(k): i for i, k in enumerate(kfs)}
-    K = np.zeros(len(kfs), BA_KF_DTYPE)
-    for i, k in enumerate(kfs):
-        K[i]["tcw"] = np.asarray(k.tcw, np.float32).reshape(-1)
-        K[i]["id"] = k.id
-        K[i]["fixed"] = 1 if (i >= len(local_kfs) or k.id == 0) else 0
-        K[i]["fx"], K[i]["fy"], K[i]["cx"], K[i]["cy"], K[i]["bf"] = k.cam.fx, k.cam.fy, k.cam.cx, k.cam.cy, k.cam.bf
-    P = np.zeros(len(local_mps), BA_PT_DTYPE)
-    if local_mps:
-        P["pos"] = np.array([mp.pos for mp in local_mps], np.float32)
-        P["id"] = [mp.id for mp in local_mps]
-        P["bad"] = [int(mp.bad) for mp in local_mps]
-    e_pt, e_kf, e_kp = [], [], []
-    for pi, mp in enumerate(local_mps):
-        for kf in sorted(mp.observations, key=lambda k: k.id):
-            ki = kidx.get(id(kf))
-            if kf.bad or ki is None:
-                continue
-            e_pt.append(pi)
-            e_kf.append(ki)
-            e_kp.append(mp.observations[kf])
-    E = np.zeros(len(e_pt), BA_EDGE_DTYPE)
-    if e_pt:
-        E["point"], E["kf"] = e_pt, e_kf
-        e_kf, e_kp = np.asarray(e_kf), np.asarray(e_kp)
-        for ki in np.unique(e_kf):   # one gather per keyframe
-            sel = e_kf == ki
-            k, j = kfs[ki], e_kp[sel]
-            kp = k.keys_un[j]
-            E["u"][sel] = kp["x"]
-            E["v"][sel] = kp["y"]
-            E["ur"][sel] = np.asarray(k.u_right, np.float32)[j]
-            E[E.dtype.names[5]][sel] = np.asarray(k.inv_level_sigma2, np.float32)[kp["octave"]]
+    K = _ba_keyframes(kfs, lambda i, k: i >= len(local_kfs) or k.id == 0)
+    P, E = _ba_points_edges(local_mps, kfs)
     return BAProblem(K, P, E), kfs, local_mps
 
 

@@ -76,6 +76,48 @@ def test_gba_deterministic(GBA):
     assert (a["iterations"], a["status"], a["checks"]) == (b["iterations"], b["status"], b["checks"])
 
 
+def _same_bits(a, b):
+    assert set(a) == set(b)
+    for k in set(a) - {"phase_ms"}:
+        if isinstance(a[k], np.ndarray):
+            assert a[k].dtype == b[k].dtype and a[k].shape == b[k].shape and a[k].tobytes() == b[k].tobytes(), k
+        elif isinstance(a[k], (float, tuple)):
+            assert np.asarray(a[k], np.float64).tobytes() == np.asarray(b[k], np.float64).tobytes(), k
+        else:
+            assert a[k] == b[k], k
+
+
+def test_both_entries_on_one_handle():
+    """Global BA and LocalBA share a handle's device arena (and its stream): a large global problem,
+    LocalBA, a small global problem and LocalBA again on one handle give, array for array and bit
+    for bit, what each call gives on a fresh handle -- nothing one entry leaves in the arena or in
+    the pinned buffers reaches the other."""
+    from orb_slam2_with_comment_amd import synth_map as SM
+    from orb_slam2_with_comment_amd.optimizer import GlobalBA, LocalBA
+    (big, big_it, big_rob), (small, small_it, small_rob) = [(b(), it, rob) for b, it, rob in
+                                                            (GS.CASES["free17_robust"], GS.CASES["free3"])]
+    local = SM.local_ba_problem(seed=3, n_free=6, n_fixed=2, n_points=300)[0]
+    calls = [lambda g: g.run(big, big_it, big_rob), lambda g: LocalBA.run(g, local),
+             lambda g: g.run(small, small_it, small_rob), lambda g: LocalBA.run(g, local)]
+
+    def fresh(call):
+        g = GlobalBA()
+        try:
+            return call(g)
+        finally:
+            g.close()
+    want = [fresh(c) for c in calls[:3]]
+    want.append(want[1])  # the same LocalBA call
+    g = GlobalBA()
+    try:
+        got = [c(g) for c in calls]
+    finally:
+        g.close()
+    assert want[0]["n_free"] == 17 and want[2]["n_free"] == 3 and want[1]["iterations"][0] > 0
+    for a, b in zip(got, want):
+        _same_bits(a, b)
+
+
 def _check_689(oracle, prob):
     """The index of the src/Optimizer.cc:689 check: the first k at which LocalBA's oracle stops
     after the robust optimize(5) alone."""

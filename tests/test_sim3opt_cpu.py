@@ -253,6 +253,111 @@ def test_host_header_under_sanitizers():
         assert got["cnt"][0] == solved(spec).n_in
 
 
+# ---- the one Levenberg decision (csrc/g2o_lm.h) over a table of steps, once per cube -----------------
+
+DBL_MAX = 1.7976931348623157e308
+# (kind, ...): n lambda0 = a new optimize(); b chi = lm_begin; t ok2 tempChi scale_sum = lm_trial; e = lm_end
+LM_TABLE = [
+    ("n", 0.5),
+    ("b", 100.0), ("t", 1, 40.0, 59.999), ("e",),                  # an accept with rho near 1: lambda / 3
+    ("b", 40.0), ("t", 1, 30.0, 19.999), ("e",),                   # rho 0.5: alpha = 1, clamped at 2/3
+    ("b", 30.0), ("t", 1, 35.0, 10.0),                             # a reject
+    ("t", 0, 29.0, 10.0),                                          # a failed solve
+    ("t", 1, float("inf"), 10.0),                                  # a non-finite tempChi
+    ("t", 1, 29.0, 10.0), ("e",),
+    ("b", 29.0), ("t", 1, float("nan"), 10.0), ("e",),             # NaN: rho is NaN, the do-while ends
+    ("b", 29.0)] + [("t", 1, 31.0 + k, 10.0) for k in range(10)] + [("e",),   # ten rejections in a row: Terminate
+    ("n", 1.0),
+    ("b", 30.0), ("t", 1, 21.041, 10.0), ("e",),                   # z = 2 rho - 1 whose two cubes differ in the last bit
+    ("n", 1e-16),
+    ("b", 7.0), ("t", 1, 7.0, 3.0), ("e",),                        # rho = 0: Terminate
+    ("n", 2.0),
+    ("b", 1000.0), ("t", 1, 999.5, 2.0), ("e",),                   # three small-gain iterations in a row
+    ("b", 999.5), ("t", 1, 999.0, 2.0), ("e",),
+    ("b", 999.0), ("t", 1, 998.5, 2.0), ("e",)]
+
+
+def lm_restated(cube):
+    """g2o's OptimizationAlgorithmLevenberg::solve decision, written out in Python floats."""
+    bits = lambda v: struct.pack(">d", v).hex()
+    lines, L, it, lambda0 = [], None, 0, 0.0
+
+    def state(what, v0, v1):
+        lines.append("%s %s %s %s %s %d %d %d %d" % (what, bits(L["lambda"]), bits(L["ni"]), bits(L["rho"]),
+                                                     bits(L["chi"]), L["qmax"], L["nBad"], v0, v1))
+    for s in LM_TABLE:
+        if s[0] == "n":
+            L, it, lambda0 = {"lambda": 0.0, "ni": 0.0, "chi": 0.0, "ini": 0.0, "rho": 0.0, "qmax": 0, "nBad": 0}, 0, s[1]
+        elif s[0] == "b":
+            L["chi"] = L["ini"] = s[1]
+            if it == 0:
+                L["lambda"], L["ni"], L["nBad"] = lambda0, 2.0, 0
+            L["rho"], L["qmax"] = 0.0, 0
+            state("b", 0, 0)
+        elif s[0] == "t":
+            ok2, temp, scale_sum = s[1:]
+            if not ok2:
+                temp = DBL_MAX
+            scale = scale_sum + 1e-3
+            L["rho"] = (L["chi"] - temp) / scale
+            accept = L["rho"] > 0 and np.isfinite(temp)
+            if accept:
+                alpha = 1. - cube(2 * L["rho"] - 1)
+                alpha = min(alpha, 2. / 3.)
+                L["lambda"] *= max(1. / 3., alpha)
+                L["ni"] = 2.0
+                L["chi"] = temp
+            else:
+                L["lambda"] *= L["ni"]
+                L["ni"] *= 2
+            L["qmax"] += 1
+            state("t", accept, L["rho"] < 0 and L["qmax"] < 10)
+        else:
+            stop = L["qmax"] == 10 or L["rho"] == 0
+            if not stop:
+                L["nBad"] = L["nBad"] + 1 if (L["ini"] - L["chi"]) * 1e3 < L["ini"] else 0
+                stop = L["nBad"] >= 3
+            state("e", stop, 0)
+            it += 1
+    return lines
+
+
+def test_levenberg_decision_table():
+    import math
+    exe = check_program()
+    d = os.path.dirname(exe)
+    inp, out = os.path.join(d, "lm_in.txt"), os.path.join(d, "lm_out.txt")
+    hexd = lambda v: struct.pack(">d", v).hex()
+    with open(inp, "w") as f:
+        for s in LM_TABLE:
+            f.write(" ".join([s[0]] + [str(v) if isinstance(v, int) else hexd(v) for v in s[1:]]) + "\n")
+    subprocess.run([exe, "lm", inp, out], check=True, capture_output=True)
+    got = {"mul": [], "pow": []}
+    for line in open(out).read().splitlines():
+        tag, rest = line.split(" ", 1)
+        got[tag].append(rest)
+    want = {"mul": lm_restated(lambda z: z * z * z), "pow": lm_restated(lambda z: math.pow(z, 3))}
+    for tag in ("mul", "pow"):
+        assert got[tag] == want[tag], tag
+    # the table takes every path it is written for
+    t = [l.split() for l in want["mul"]]
+    trials = [l for l in t if l[0] == "t"]
+    ends = [l for l in t if l[0] == "e"]
+    assert trials[0][7:] == ["1", "0"] and trials[0][1] == struct.pack(">d", 0.5 * (1. / 3.)).hex()   # rho near 1: lambda / 3
+    assert trials[1][1] == struct.pack(">d", 0.5 * (1. / 3.) * (2. / 3.)).hex()                        # alpha clamped at 2/3
+    assert [l[7:] for l in trials[2:6]] == [["0", "1"], ["0", "1"], ["0", "1"], ["1", "0"]]            # reject, failed, inf, accept
+    assert trials[6][3] == struct.pack(">d", float("nan")).hex() and trials[6][7:] == ["0", "0"]       # NaN
+    assert [l[7:] for l in trials[7:17]] == [["0", "1"]] * 9 + [["0", "0"]] and ends[4][7] == "1"      # ten rejections
+    assert trials[18][3] == struct.pack(">d", 0.0).hex() and ends[6][7] == "1"                         # rho = 0
+    assert [l[6] + l[7] for l in ends[7:10]] == ["10", "20", "31"]                                     # nBad 1, 2, 3: Terminate
+    # the two cubes part in the last bit of lambda on the step built for it, and nowhere else
+    differ = [i for i, (a, b) in enumerate(zip(want["mul"], want["pow"])) if a != b]
+    step = [i for i, l in enumerate(t) if l[0] == "t"][17]
+    assert differ and differ[0] == step and want["mul"][step].split()[7] == "1"
+    lam = [int(w[step].split()[1], 16) for w in (want["mul"], want["pow"])]
+    assert abs(lam[0] - lam[1]) == 1
+
+
 # ---- the Python assembly of OptimizeSim3 ----------------------------------------------------------
 
 def _two_keyframes(n=40, seed=3):
