@@ -56,15 +56,10 @@ int orbmi_extract(orbmi_extractor* h, const uint8_t* image, int rows, int cols, 
     ORBMI_HIP(hipSetDevice(e.device));  // buffers grown below belong to the handle's device
     int rc;
     if ((rc = e.set_geometry(rows, cols))) return rc;
-    const int cap = std::max(capacity, e.nfeatures + 64);
+    const int cap = std::max(capacity, e.tab.nfeatures + 64);
     if ((rc = e.reserve(1, cap))) return rc;
     const size_t bytes = (size_t)rows * cols;
-    if (bytes > e.image_bytes) {
-        if (e.d_image) (void)hipFree(e.d_image);
-        e.d_image = nullptr;
-        ORBMI_HIP(hipMalloc((void**)&e.d_image, bytes));
-        e.image_bytes = bytes;
-    }
+    if ((rc = orbmi::ensure_buf(&e.d_image, &e.image_bytes, bytes))) return rc;
     // a contiguous image goes as one copy (a pitched copy from pageable memory runs row by row)
     if (step == (size_t)cols) ORBMI_HIP(hipMemcpyAsync(e.d_image, image, bytes, hipMemcpyHostToDevice, e.stream));
     else ORBMI_HIP(hipMemcpy2DAsync(e.d_image, cols, image, step, cols, rows, hipMemcpyHostToDevice, e.stream));
@@ -119,8 +114,8 @@ int orbmi_extractor_synchronize(orbmi_extractor* h) {
     return ORBMI_OK;
 }
 
-int orbmi_extractor_get_levels(const orbmi_extractor* h) { return h ? h->ex.nlevels : ORBMI_E_ARG; }
-float orbmi_extractor_get_scale_factor(const orbmi_extractor* h) { return h ? h->ex.scale_factor : 0.f; }
+int orbmi_extractor_get_levels(const orbmi_extractor* h) { return h ? h->ex.tab.nlevels : ORBMI_E_ARG; }
+float orbmi_extractor_get_scale_factor(const orbmi_extractor* h) { return h ? h->ex.tab.scale_factor : 0.f; }
 
 static int copy_levels(const orbmi_extractor* h, const std::vector<float>& v, float* out) {
     if (!h || !out) return ORBMI_E_ARG;
@@ -128,20 +123,20 @@ static int copy_levels(const orbmi_extractor* h, const std::vector<float>& v, fl
     return ORBMI_OK;
 }
 int orbmi_extractor_get_scale_factors(const orbmi_extractor* h, float* out) {
-    return h ? copy_levels(h, h->ex.scale, out) : ORBMI_E_ARG;
+    return h ? copy_levels(h, h->ex.tab.scale, out) : ORBMI_E_ARG;
 }
 int orbmi_extractor_get_inverse_scale_factors(const orbmi_extractor* h, float* out) {
-    return h ? copy_levels(h, h->ex.inv_scale, out) : ORBMI_E_ARG;
+    return h ? copy_levels(h, h->ex.tab.inv_scale, out) : ORBMI_E_ARG;
 }
 int orbmi_extractor_get_scale_sigma_squares(const orbmi_extractor* h, float* out) {
-    return h ? copy_levels(h, h->ex.sigma2, out) : ORBMI_E_ARG;
+    return h ? copy_levels(h, h->ex.tab.sigma2, out) : ORBMI_E_ARG;
 }
 int orbmi_extractor_get_inverse_scale_sigma_squares(const orbmi_extractor* h, float* out) {
-    return h ? copy_levels(h, h->ex.inv_sigma2, out) : ORBMI_E_ARG;
+    return h ? copy_levels(h, h->ex.tab.inv_sigma2, out) : ORBMI_E_ARG;
 }
 int orbmi_extractor_get_features_per_level(const orbmi_extractor* h, int* out) {
     if (!h || !out) return ORBMI_E_ARG;
-    std::copy(h->ex.nfeat.begin(), h->ex.nfeat.end(), out);
+    std::copy(h->ex.tab.nfeat.begin(), h->ex.tab.nfeat.end(), out);
     return ORBMI_OK;
 }
 
@@ -149,12 +144,12 @@ int orbmi_extractor_get_pyramid_level(orbmi_extractor* h, int item, int level, i
                                       uint8_t* out, size_t out_step, int* w, int* hgt) {
     if (!h || !out || !w || !hgt) return ORBMI_E_ARG;
     Extractor& e = h->ex;
-    if (e.levels.empty() || item < 0 || item >= e.last_batch) return ORBMI_E_STATE;
-    if (level < 0 || level >= e.nlevels) return ORBMI_E_ARG;
-    const orbmi::LevelGeom& g = e.levels[level];
+    if (e.plan.levels.empty() || item < 0 || item >= e.last_batch) return ORBMI_E_STATE;
+    if (level < 0 || level >= e.tab.nlevels) return ORBMI_E_ARG;
+    const orbmi::LevelGeom& g = e.plan.levels[level];
     const int cw = padded ? g.W + 2 * orbmi::kEdge : g.W, ch = padded ? g.ph : g.H;
     if (out_step < (size_t)cw) return ORBMI_E_ARG;
-    const uint8_t* src = e.d_pyr + item * e.pimg + g.off;
+    const uint8_t* src = e.d_pyr + item * e.plan.pimg + g.off;
     if (!padded) src += (long long)orbmi::kEdge * g.stride + orbmi::kEdge;
     ORBMI_HIP(hipSetDevice(e.device));
     ORBMI_HIP(hipMemcpy2DAsync(out, out_step, src, g.stride, cw, ch, hipMemcpyDeviceToHost, e.stream));
@@ -171,16 +166,15 @@ int orbmi_compute_stereo_matches(orbmi_extractor* left, int item_left, orbmi_ext
     Extractor& L = left->ex;
     Extractor& R = right->ex;
     if (L.device != R.device) return ORBMI_E_ARG;
-    if (L.levels.empty() || R.levels.empty() || item_left >= L.last_batch || item_right >= R.last_batch ||
+    if (L.plan.levels.empty() || R.plan.levels.empty() || item_left >= L.last_batch || item_right >= R.last_batch ||
         item_left < 0 || item_right < 0)
         return ORBMI_E_STATE;
-    if (L.rows != R.rows || L.cols != R.cols || L.nlevels != R.nlevels) return ORBMI_E_ARG;
+    if (L.rows != R.rows || L.cols != R.cols || L.tab.nlevels != R.tab.nlevels) return ORBMI_E_ARG;
     ORBMI_HIP(hipSetDevice(L.device));
     const int cap = L.last_capacity;
-    size_t ucap = L.stereo_cap;
     int rc0;
-    if ((rc0 = orbmi::ensure_buf(&L.d_stereo_u, &ucap, (size_t)cap))) return rc0;
-    if ((rc0 = orbmi::ensure_buf(&L.d_stereo_d, &L.stereo_cap, (size_t)cap))) return rc0;
+    if ((rc0 = orbmi::ensure_buf(&L.d_stereo_u, &L.stereo_u_cap, (size_t)cap))) return rc0;
+    if ((rc0 = orbmi::ensure_buf(&L.d_stereo_d, &L.stereo_d_cap, (size_t)cap))) return rc0;
     // the right handle's work must be visible to the left handle's stream
     if (&L != &R) ORBMI_HIP(hipStreamSynchronize(R.stream));
     int rc = orbmi::stereo_run(L, item_left, R, item_right, bf, fx, L.d_stereo_u, L.d_stereo_d, cap);
@@ -202,7 +196,7 @@ int orbmi_compute_stereo_matches_batch_device(orbmi_extractor* h, float bf, floa
                                               float* d_depth) {
     if (!h || !d_u_right || !d_depth) return ORBMI_E_ARG;
     Extractor& e = h->ex;
-    if (e.last_batch < 2) return ORBMI_E_STATE;
+    if (e.plan.levels.empty() || e.last_batch < 2) return ORBMI_E_STATE;
     for (int p = 0; p + 1 < e.last_batch; p += 2) {
         const long long o = (long long)p * e.last_capacity;
         int rc = orbmi::stereo_run(e, p, e, p + 1, bf, fx, d_u_right + o, d_depth + o, e.last_capacity);
@@ -308,7 +302,7 @@ int orbmi_compute_stereo_from_rgbd(orbmi_extractor* h, int item, const void* dep
         !rgbd_depth_ok(depth, depth_type, depth_step_bytes, rows, cols))
         return ORBMI_E_ARG;
     Extractor& e = h->ex;
-    if (e.levels.empty() || item < 0 || item >= e.last_batch || !e.last_kps || !e.last_counts) return ORBMI_E_STATE;
+    if (e.plan.levels.empty() || item < 0 || item >= e.last_batch || !e.last_kps || !e.last_counts) return ORBMI_E_STATE;
     if (rows != e.rows || cols != e.cols) return ORBMI_E_ARG;
     ORBMI_HIP(hipSetDevice(e.device));
     int nk = 0;
@@ -404,19 +398,19 @@ extern "C" int orbmi_debug_fast_candidates(orbmi_extractor* h, int item, int lev
                                            int* n_out) {
     if (!h || !n_out || (cap > 0 && !xyr)) return ORBMI_E_ARG;
     Extractor& e = h->ex;
-    if (e.levels.empty() || item < 0 || item >= e.last_batch || level < 0 || level >= e.nlevels)
+    if (e.plan.levels.empty() || item < 0 || item >= e.last_batch || level < 0 || level >= e.tab.nlevels)
         return ORBMI_E_STATE;
     ORBMI_HIP(hipSetDevice(e.device));
     ORBMI_HIP(hipStreamSynchronize(e.stream));
     int rc_[orbmi::kFastRegions];
-    ORBMI_HIP(hipMemcpy(rc_, e.d_level_count + ((size_t)item * e.nlevels + level) * orbmi::kFastRegions,
+    ORBMI_HIP(hipMemcpy(rc_, e.d_level_count + ((size_t)item * e.tab.nlevels + level) * orbmi::kFastRegions,
                         sizeof(rc_), hipMemcpyDeviceToHost));
     std::vector<uint2> cand;
     for (int j = 0; j < orbmi::kFastRegions; j++) {
         if (rc_[j] <= 0) continue;
         const size_t at = cand.size();
         cand.resize(at + rc_[j]);
-        ORBMI_HIP(hipMemcpy(cand.data() + at, e.d_cand + (size_t)item * e.keys_cap + e.regbase[level * orbmi::kFastRegions + j],
+        ORBMI_HIP(hipMemcpy(cand.data() + at, e.d_cand + (size_t)item * e.plan.keys_cap + e.plan.regbase[level * orbmi::kFastRegions + j],
                             rc_[j] * sizeof(uint2), hipMemcpyDeviceToHost));
     }
     const int count = (int)cand.size();
@@ -438,13 +432,13 @@ extern "C" int orbmi_debug_set_keypoints(orbmi_extractor* h, int item, const orb
                                          const uint8_t* desc, int n) {
     if (!h || n < 0 || (n > 0 && (!kps || !desc))) return ORBMI_E_ARG;
     Extractor& e = h->ex;
-    if (e.levels.empty() || !e.last_kps || !e.last_desc || !e.last_counts || item < 0 || item >= e.last_batch)
+    if (e.plan.levels.empty() || !e.last_kps || !e.last_desc || !e.last_counts || item < 0 || item >= e.last_batch)
         return ORBMI_E_STATE;
     if (n > e.last_capacity) return ORBMI_E_CAP;
     // the stereo kernels index the scale table and the levels by octave and the row table by y
     for (int i = 0; i < n; i++) {
         const orbmi_keypoint& k = kps[i];
-        if (k.octave < 0 || k.octave >= e.nlevels || !(k.x >= 0.f && k.x <= (float)(e.cols - 1)) ||
+        if (k.octave < 0 || k.octave >= e.tab.nlevels || !(k.x >= 0.f && k.x <= (float)(e.cols - 1)) ||
             !(k.y >= 0.f && k.y <= (float)(e.rows - 1)))
             return ORBMI_E_ARG;
     }
@@ -463,16 +457,16 @@ extern "C" int orbmi_debug_set_keypoints(orbmi_extractor* h, int item, const orb
 extern "C" int orbmi_debug_octree_level(orbmi_extractor* h, int item, int level, int* xyr, int cap, int* n_out) {
     if (!h || !n_out || (cap > 0 && !xyr)) return ORBMI_E_ARG;
     Extractor& e = h->ex;
-    if (e.levels.empty() || item < 0 || item >= e.last_batch || level < 0 || level >= e.nlevels)
+    if (e.plan.levels.empty() || item < 0 || item >= e.last_batch || level < 0 || level >= e.tab.nlevels)
         return ORBMI_E_STATE;
     ORBMI_HIP(hipSetDevice(e.device));
     ORBMI_HIP(hipStreamSynchronize(e.stream));
-    const orbmi::LevelGeom& g = e.levels[level];
+    const orbmi::LevelGeom& g = e.plan.levels[level];
     int n = 0;
-    ORBMI_HIP(hipMemcpy(&n, e.d_oct_count + (size_t)item * e.nlevels + level, sizeof(int), hipMemcpyDeviceToHost));
+    ORBMI_HIP(hipMemcpy(&n, e.d_oct_count + (size_t)item * e.tab.nlevels + level, sizeof(int), hipMemcpyDeviceToHost));
     std::vector<uint2> v(std::max(n, 1));
     if (n > 0)
-        ORBMI_HIP(hipMemcpy(v.data(), e.d_oct + (size_t)item * e.out_cap + g.out_base, n * sizeof(uint2),
+        ORBMI_HIP(hipMemcpy(v.data(), e.d_oct + (size_t)item * e.plan.out_cap + g.out_base, n * sizeof(uint2),
                             hipMemcpyDeviceToHost));
     for (int i = 0; i < n && i < cap; i++) {
         xyr[3 * i] = v[i].x & 0xFFFF;

@@ -1,55 +1,15 @@
-// Host-side runtime of the device ORB extractor (shared by extractor.hip, stereo.hip, capi.cpp).
+// The extractor's handle (shared by extractor.hip, stereo.hip, capi_extract.cpp): the tables and the
+// plan of the current image size (extractor_plan.h, HIP-free: everything the host computes), their
+// device mirrors, and the grow-only device buffers.
 #pragma once
+#include <array>
 #include <vector>
 
 #include "orbmi_common.h"
 
 namespace orbmi {
 
-// Per pyramid level constants, resident in device memory (one copy per handle geometry).
-struct LevelGeom {
-    int W, H;            // interior size  (ComputePyramid :1111-1112)
-    int stride, ph;      // padded row pitch (>= W+38, 64-aligned) and padded height H+38
-    long long off;       // byte offset of the padded level inside one image's pyramid
-    int cell_begin, cell_end;   // FAST cell range (global cell index)
-    int nfeat;           // mnFeaturesPerLevel[level]
-    int out_base, out_cap;      // octree output slots (per image)
-    int key_base, key_cap;      // candidate scratch (per image)
-    int width, height;   // octree area maxBorderX-minBorderX, maxBorderY-minBorderY
-    int nIni;            // DistributeOctTree initial node count
-    float hX;            // (float)width / nIni
-    float scale;         // mvScaleFactor[level]
-    float size;          // (float)(int)(PATCH_SIZE * scale)
-    int blur_xv;         // first column of the GaussianBlur scalar tail (4*floor(W/4))
-    int resize_xv;       // first column of the resize vertical scalar tail
-    int xtab_off, ytab_off;     // offsets into the resize coefficient tables (level >= 1)
-    long long boff;      // byte offset of the blurred level (interior only) inside one image's blur
-    int bstride;         // blurred row pitch (W rounded up to 128)
-};
-
-// One FAST cell of ComputeKeyPointsOctTree (src/ORBextractor.cc:789-829).
-struct CellGeom {
-    short x0, y0, w, h;  // ROI in interior coordinates; w == 0 -> skipped cell
-    short sx, sy;        // j*wCell, i*hCell shift added to ROI coordinates
-    int slot_base;       // base of the cell's candidate region (per image; cells of one level
-                         // share kFastRegions regions, cell k of the level writes region k % R)
-    int level;
-    long long roi_off;   // byte offset of the ROI's first pixel in one image's pyramid (level plane,
-                         // border, stride folded in: k_fast2 needs no LevelGeom load)
-    int stride;          // the level's row stride
-    int lcell;           // index of the cell within its level
-};
-
-struct XTab { short sx0, sx1, a0, a1; };  // horizontal resize: source taps and 11-bit weights
-struct YTab { short y0, y1, b0, b1; };    // vertical resize
-struct PyrRect { short x0, x1, y0, y1; };  // half-open interior rectangle of one level
-struct PyrTile { PyrRect own, need; };     // k_pyramid tile of one level: written to HBM / computed in LDS
-
-constexpr int kOctNodeCap = 2048;  // live quadtree nodes per level held in LDS
-constexpr int kFastRegions = 16;   // candidate regions per level (spreads k_fast2's allocation atomics)
-constexpr int kBlurTW = 128, kBlurTH = 32;  // GaussianBlur output tile
-
-// Grow-only device buffer.
+// Grow-only device buffer.  On failure *p is null and *cap is 0: the next call allocates again.
 template <class T>
 inline int ensure_buf(T** p, size_t* cap, size_t n) {
     if (*p && *cap >= n) return ORBMI_OK;
@@ -64,19 +24,12 @@ inline int ensure_buf(T** p, size_t* cap, size_t n) {
 
 struct Extractor {
     int device = 0;
-    int nfeatures = 0, nlevels = 0, ini_th = 0, min_th = 0;
-    float scale_factor = 0.f;
-    std::vector<float> scale, inv_scale, sigma2, inv_sigma2;
-    std::vector<int> nfeat, umax;
-
-    // geometry for the current image size
+    int ini_th = 0, min_th = 0;
+    OrbTables tab;       // of the constructor's parameters
+    // The geometry of the current image size.  rows == cols == 0 and an empty plan: none, and
+    // set_geometry plans again; otherwise the device mirrors below hold exactly this plan.
     int rows = 0, cols = 0;
-    std::vector<LevelGeom> levels;
-    std::vector<CellGeom> cells;
-    std::vector<int2> btiles;
-    long long pimg = 0;      // bytes of one padded pyramid
-    long long bimg = 0;      // bytes of one blurred pyramid
-    int keys_cap = 0, out_cap = 0;
+    ExtractorPlan plan;
     int blur_mode = -1;  // GaussianBlur (ORBMI_BLUR): -1 by batch, 0 side stream, 1 in the octree launch, 2 after it
     hipStream_t bstream = nullptr;  // the blur's side stream
     hipEvent_t ev_pyr = nullptr, ev_blur = nullptr;
@@ -91,14 +44,9 @@ struct Extractor {
     uint8_t* d_pyr = nullptr;
     uint8_t* d_blur = nullptr;     // blurred levels: interior only, rows of bstride bytes
     int2* d_btiles = nullptr;      // blur tiles: {level, x0 | y0 << 16}
-    int nbtiles = 0;
-    int fast_maxw = 0, fast_maxh = 0;  // largest cell ROI (k_fast2's LDS per wave)
     int* d_level_count = nullptr;   // [b][level][region] FAST candidates (k_fast2 allocates, k_pyr_level0 clears)
     int* d_regbase = nullptr;       // [level][region] first slot of each candidate region (per image)
-    std::vector<uint32_t> pyr_blob; // k_pyramid parameter blocks, pyr_blob_words per tile
-    uint32_t* d_pyr_blob = nullptr;
-    int pyr_kx = 0, pyr_ky = 0, pyr_hx = 0, pyr_hy = 0, pyr_blob_words = 0, pyr_lds0 = 0, pyr_lds_half = 0;
-    std::vector<int> regbase;
+    uint32_t* d_pyr_blob = nullptr; // k_pyramid parameter blocks, plan.blob_words per tile
     uint2* d_cand = nullptr;        // [b][keys_cap] {x | y << 12 | score << 24, cell << 10 | rank}
     uint32_t* d_node_of = nullptr;  // octree node | depth << 16 of keys beyond the register-resident ones
     uint2* d_oct = nullptr;        // {x | y << 16 (level coords), score}
@@ -127,7 +75,7 @@ struct Extractor {
     int* d_row_start = nullptr;
     int* d_row_list = nullptr;
     int* d_sad = nullptr;
-    size_t row_cap = 0, row_list_cap = 0, sad_cap = 0, stereo_cap = 0;
+    size_t row_cap = 0, row_list_cap = 0, sad_cap = 0, stereo_u_cap = 0, stereo_d_cap = 0;
     float* d_stereo_u = nullptr;
     float* d_stereo_d = nullptr;
 
@@ -139,6 +87,9 @@ struct Extractor {
     hipEvent_t prof_event();
     hipEvent_t prof_begin(int stage, hipStream_t s = nullptr);
     void prof_end(int stage, hipEvent_t a, hipStream_t s = nullptr);
+
+    struct GeomTable { void** dev; const void* host; size_t bytes; };
+    std::array<GeomTable, 7> geom_tables(const ExtractorPlan& p);  // the plan's tables and their device mirrors
 
     int init(int dev, int nf, float sf, int nl, int ini, int mn);
     int set_geometry(int rows, int cols);

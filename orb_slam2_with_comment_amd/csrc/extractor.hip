@@ -13,6 +13,7 @@
 // Results are bit-exact with the pinned CPU restatement (oracle/, DESIGN.md "Pinned semantics").
 #include <algorithm>
 #include <cmath>
+#include <cstddef>
 #include <cstdlib>
 #include <cstring>
 
@@ -32,36 +33,11 @@ namespace orbmi {
 // rectangle reads (host-built, PyrTile), so the levels chain inside the workgroup with one
 // barrier per level and no HBM round trip.  Halo pixels are computed by every tile that needs
 // them, with the same formula.
-__device__ inline void pyr_store(uint8_t* lvl, int W, int H, int stride, int x, int y, uint8_t v) {
-    // interior (x, y) and every border pixel mirroring it (one reflection: W, H > kEdge)
-    int xs[3], ys[3], nx = 0, ny = 0;
-    xs[nx++] = x;
-    if (x >= 1 && x <= kEdge) xs[nx++] = -x;
-    if (x >= W - 1 - kEdge && x <= W - 2) xs[nx++] = 2 * W - 2 - x;
-    ys[ny++] = y;
-    if (y >= 1 && y <= kEdge) ys[ny++] = -y;
-    if (y >= H - 1 - kEdge && y <= H - 2) ys[ny++] = 2 * H - 2 - y;
-    for (int j = 0; j < ny; j++)
-        for (int i = 0; i < nx; i++) lvl[(long long)(ys[j] + kEdge) * stride + xs[i] + kEdge] = v;
-}
-
-// cv::resize INTER_LINEAR 8U of one pixel from its four taps (pinned P2: the SSE2 vertical pass
-// for x < resize_xv, the scalar tail after it).
-__device__ inline int pyr_resize_px(int p00, int p01, int p10, int p11, const XTab& x, const YTab& y, bool vec) {
-    const int h0 = p00 * x.a0 + p01 * x.a1;
-    const int h1 = p10 * x.a0 + p11 * x.a1;
-    int v;
-    if (vec)  // VResizeLinearVec_32s8u lanes
-        v = ((((h0 >> 4) * y.b0) >> 16) + (((h1 >> 4) * y.b1) >> 16) + 2) >> 2;
-    else
-        v = (h0 * y.b0 + h1 * y.b1 + (1 << 21)) >> 22;
-    return v < 0 ? 0 : (v > 255 ? 255 : v);
-}
+// pyr_store and pyr_resize_px (extractor_plan.h) are shared with the CPU run of the tile plan.
 
 constexpr int kPyrThreads = 1024;  // 64 columns x 16 rows per step
 constexpr int kPyrRows = kPyrThreads / 64;
 constexpr int kPyrTiledMaxBatch = 8;  // larger batches build the pyramid level by level
-constexpr int kPyrLevelWords = 10; // per level in a tile's parameter block (PyrBlob, host)
 
 // global -> LDS copy of n elements with kInFlight loads issued before the first store
 template <int kInFlight, class T, class F>
@@ -115,20 +91,20 @@ __global__ __launch_bounds__(kPyrThreads) void k_pyramid(const uint8_t* __restri
     auto hi16 = [](uint32_t w) { return (int)(short)(w >> 16); };
     {   // level 0: the own rectangle with its border mirrors
         const uint32_t* G = B;
-        const int W = lo16(G[4]), H = hi16(G[4]), stride = (int)G[5];
-        uint8_t* lvl = P + G[6];
+        const int W = lo16(G[kPyrWH]), H = hi16(G[kPyrWH]), stride = (int)G[kPyrStride];
+        uint8_t* lvl = P + G[kPyrOff];
         for (int y = oy0 + ty; y < oy1; y += kPyrRows)
             for (int x = ox0 + tx; x < ox1; x += 64) pyr_store(lvl, W, H, stride, x, y, L0[(y - ny0) * w0 + x - nx0]);
     }
     int snx0 = nx0, sny0 = ny0, sw = w0;  // the source need rectangle of the next level
     for (int l = 1; l < nlevels; l++) {
         const uint32_t* G = B + l * kPyrLevelWords;
-        const int o_x0 = lo16(G[0]), o_x1 = hi16(G[0]), o_y0 = lo16(G[1]), o_y1 = hi16(G[1]);
-        const int n_x0 = lo16(G[2]), n_x1 = hi16(G[2]), n_y0 = lo16(G[3]), n_y1 = hi16(G[3]);
-        const int W = lo16(G[4]), H = hi16(G[4]), stride = (int)G[5], rxv = (int)G[7];
-        uint8_t* lvl = P + G[6];
-        const uint32_t* XT = B + G[8];  // 2 words per column of the need rectangle
-        const uint32_t* YT = B + G[9];  // 2 words per row
+        const int o_x0 = lo16(G[kPyrOwnX]), o_x1 = hi16(G[kPyrOwnX]), o_y0 = lo16(G[kPyrOwnY]), o_y1 = hi16(G[kPyrOwnY]);
+        const int n_x0 = lo16(G[kPyrNeedX]), n_x1 = hi16(G[kPyrNeedX]), n_y0 = lo16(G[kPyrNeedY]), n_y1 = hi16(G[kPyrNeedY]);
+        const int W = lo16(G[kPyrWH]), H = hi16(G[kPyrWH]), stride = (int)G[kPyrStride], rxv = (int)G[kPyrResizeXv];
+        uint8_t* lvl = P + G[kPyrOff];
+        const uint32_t* XT = B + G[kPyrXTaps];  // 2 words per column of the need rectangle
+        const uint32_t* YT = B + G[kPyrYTaps];  // 2 words per row
         const uint8_t* src = l == 1 ? L0 : H2 + ((l - 1) & 1) * lds_half;
         uint8_t* dst = H2 + (l & 1) * lds_half;
         const int nw = n_x1 - n_x0;
@@ -266,7 +242,6 @@ __device__ inline bool xcd_image_map(int nimg, int& unit, int& img) {
 }
 
 // ------------------------------------------------------------------------------ FAST
-constexpr int kTile = 64;               // max cell ROI edge (wCell+6, hCell+6): it fits k_fast2<80>'s tile
 constexpr int kFastCells = 2;           // waves (cells) per workgroup
 
 // LDS writes of this wave visible to its own later reads (wave-private LDS regions)
@@ -1247,7 +1222,6 @@ constexpr int kDescTargetWG = 1536;                   // workgroups per launch (
 #endif
 constexpr int kBP = ORBMI_DESC_BP;                    // LDS pitch: 37 bytes from any 8-B phase need 44
 constexpr int kBQ = kBP / 8;                          // 8-B loads per window row
-constexpr int kIcItems = 224;                         // IC dwords per phase (<= 213 used): 14 per lane
 struct DescLevel { long long off, boff; int stride, bstride, out_base; float scale, size; };
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
@@ -1402,359 +1376,89 @@ __global__ __launch_bounds__(64 * kDescWaves) void k_describe4(const uint8_t* __
 }
 
 // ------------------------------------------------------------------------------ host
-static int cv_round_host(float v) { return (int)lrintf(v); }
+static_assert(sizeof(BlurTile) == sizeof(int2) && alignof(BlurTile) <= alignof(int2) && offsetof(BlurTile, xy) == offsetof(int2, y),
+              "k_blur reads the plan's blur tiles as int2");
+static_assert(sizeof(DescribeTables::pattern) == sizeof(float4[256]) && sizeof(DescribeTables::ic) == sizeof(uint4[4][kIcItems]),
+              "k_describe4 reads the describe tables as float4 / uint4");
 
 int Extractor::init(int dev, int nf, float sf, int nl, int ini, int mn) {
     if (nf < 0 || nl < 1 || nl > kMaxLevels || !(sf > 1.0f)) return ORBMI_E_ARG;
-    device = dev; nfeatures = nf; scale_factor = sf; nlevels = nl; ini_th = ini; min_th = mn;
+    device = dev; ini_th = ini; min_th = mn;
     ORBMI_HIP(hipSetDevice(device));
     ORBMI_HIP(orbmi::stream_create(&stream, "EXTRACTOR"));
-    // ORBextractor::ORBextractor  src/ORBextractor.cc:410-470 (same float/double steps)
-    scale.assign(nl, 1.f); sigma2.assign(nl, 1.f); inv_scale.resize(nl); inv_sigma2.resize(nl);
-    const double sfd = (double)sf;
-    for (int i = 1; i < nl; i++) {
-        scale[i] = (float)((double)scale[i - 1] * sfd);
-        sigma2[i] = scale[i] * scale[i];
-    }
-    for (int i = 0; i < nl; i++) { inv_scale[i] = 1.0f / scale[i]; inv_sigma2[i] = 1.0f / sigma2[i]; }
-    nfeat.resize(nl);
-    const float factor = (float)(1.0f / sfd);
-    float ndes = (float)nf * (1 - factor) / (1 - (float)pow((double)factor, (double)nl));
-    int sum = 0;
-    for (int l = 0; l < nl - 1; l++) { nfeat[l] = cv_round_host(ndes); sum += nfeat[l]; ndes *= factor; }
-    nfeat[nl - 1] = std::max(nf - sum, 0);
-    umax.assign(kHalfPatch + 1, 0);
-    const int vmax = cv_floor_f(kHalfPatch * sqrtf(2.f) / 2 + 1);
-    const int vmin = (int)ceilf(kHalfPatch * sqrtf(2.f) / 2);
-    const double hp2 = kHalfPatch * kHalfPatch;
-    for (int v = 0; v <= vmax; ++v) umax[v] = (int)lrint(sqrt(hp2 - v * v));
-    for (int v = kHalfPatch, v0 = 0; v >= vmin; --v) {
-        while (umax[v0] == umax[v0 + 1]) ++v0;
-        umax[v] = v0;
-        ++v0;
-    }
-    {   // k_describe4's tables: the pattern as (x0, x1, y0, y1) floats, and per 4-B phase ou of
-        // the IC patch's first byte the dwords covering each circle row with their byte weights
-        float4 pf[256];
-        for (int t = 0; t < 256; t++)  // pair t = 16 l + k at 16 k + l
-            pf[16 * (t & 15) + (t >> 4)] =
-                make_float4(ORBMI_PATTERN[t][0], ORBMI_PATTERN[t][2], ORBMI_PATTERN[t][1], ORBMI_PATTERN[t][3]);
-        ORBMI_HIP(hipMemcpyToSymbol(HIP_SYMBOL(c_pattern_f), pf, sizeof(pf)));
-        static uint4 ic[4][kIcItems];
-        memset(ic, 0, sizeof(ic));
-        for (int ou = 0; ou < 4; ou++) {
-            int n = 0;
-            for (int v = -kHalfPatch; v <= kHalfPatch; v++) {
-                const int d = umax[v < 0 ? -v : v], r = v + kHalfPatch;
-                for (int dd = (ou + kHalfPatch - d) / 4; dd <= (ou + kHalfPatch + d) / 4; dd++) {
-                    if (n >= kIcItems) return ORBMI_E_ARG;
-                    unsigned wa = 0, wm = 0;
-                    for (int p = 0; p < 4; p++) {
-                        const int u = 4 * dd + p - ou - kHalfPatch;
-                        if (u >= -d && u <= d) { wa |= (unsigned)(u + 16) << (8 * p); wm |= 1u << (8 * p); }
-                    }
-                    ic[ou][n++] = make_uint4(wa, wm, (unsigned)r, (unsigned)(4 * dd));
-                }
-            }
-        }
-        ORBMI_HIP(hipMemcpyToSymbol(HIP_SYMBOL(c_ictab), ic, sizeof(ic)));
-        const char* e = getenv("ORBMI_BLUR");
-        blur_mode = !e ? -1 : !strcmp(e, "side") ? 0 : !strcmp(e, "fused") ? 1 : !strcmp(e, "serial") ? 2 : -1;
-    }
-    std::vector<float> tab(scale);
-    tab.insert(tab.end(), inv_scale.begin(), inv_scale.end());
-    ORBMI_HIP(hipMalloc((void**)&d_scale_tab, tab.size() * sizeof(float)));
-    ORBMI_HIP(hipMemcpy(d_scale_tab, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice));
+    tab = orb_tables(nf, sf, nl);
+    DescribeTables dt;
+    const int rc = describe_tables(tab.umax, ORBMI_PATTERN, &dt);
+    if (rc) return rc;
+    ORBMI_HIP(hipMemcpyToSymbol(HIP_SYMBOL(c_pattern_f), dt.pattern, sizeof(dt.pattern)));
+    ORBMI_HIP(hipMemcpyToSymbol(HIP_SYMBOL(c_ictab), dt.ic, sizeof(dt.ic)));
+    const char* e = getenv("ORBMI_BLUR");
+    blur_mode = !e ? -1 : !strcmp(e, "side") ? 0 : !strcmp(e, "fused") ? 1 : !strcmp(e, "serial") ? 2 : -1;
+    std::vector<float> st(tab.scale);
+    st.insert(st.end(), tab.inv_scale.begin(), tab.inv_scale.end());
+    ORBMI_HIP(hipMalloc((void**)&d_scale_tab, st.size() * sizeof(float)));
+    ORBMI_HIP(hipMemcpy(d_scale_tab, st.data(), st.size() * sizeof(float), hipMemcpyHostToDevice));
     return ORBMI_OK;
 }
 
-static int resize_simd_end(int width) {
-    int x = 0;
-    while (x <= width - 16) x += 16;
-    while (x < width - 4) x += 4;
-    return x;
+// The device mirrors of a plan's tables: set_geometry fills them from this list, release frees them.
+std::array<Extractor::GeomTable, 7> Extractor::geom_tables(const ExtractorPlan& p) {
+    auto tb = [](auto** d, const auto& v) { return GeomTable{(void**)d, v.data(), v.size() * sizeof(v[0])}; };
+    return {tb(&d_levels, p.levels), tb(&d_cells, p.cells), tb(&d_regbase, p.regbase), tb(&d_pyr_blob, p.blob),
+            tb(&d_btiles, p.btiles), tb(&d_xtab, p.xtab), tb(&d_ytab, p.ytab)};
 }
 
-template <class T>
-static int dev_alloc(T** p, size_t n) {
-    if (*p) { (void)hipFree(*p); *p = nullptr; }
-    if (n == 0) n = 1;
-    ORBMI_HIP(hipMalloc((void**)p, n * sizeof(T)));
-    return ORBMI_OK;
-}
-
+// The handle either describes one geometry completely -- rows, cols, plan and the device tables
+// agree -- or is marked as having none.  A refused size leaves it as it was (the plan is built
+// into a local); once the tables of the next size start replacing the old ones the handle is
+// marked, and it takes the next geometry only after the last upload.
 int Extractor::set_geometry(int r, int c) {
-    if (r == rows && c == cols && !levels.empty()) return ORBMI_OK;
+    if (r == rows && c == cols && !plan.levels.empty()) return ORBMI_OK;
     ORBMI_HIP(hipSetDevice(device));
-    levels.assign(nlevels, LevelGeom{});
-    cells.clear();
-    std::vector<XTab> xt;
-    std::vector<YTab> yt;
-    long long off = 0, boff = 0;
-    int slot = 0, key = 0, outb = 0;
-    regbase.assign((size_t)nlevels * kFastRegions, 0);
-    for (int l = 0; l < nlevels; l++) {
-        LevelGeom& g = levels[l];
-        g.W = cv_round_host((float)c * inv_scale[l]);
-        g.H = cv_round_host((float)r * inv_scale[l]);
-        const int minB = kEdge - 3, maxBX = g.W - kEdge + 3, maxBY = g.H - kEdge + 3;
-        if (maxBX - minB < 30 || maxBY - minB < 30) return ORBMI_E_UNSUPPORTED;
-        g.stride = (g.W + 2 * kEdge + 63) & ~63;
-        g.ph = g.H + 2 * kEdge;
-        g.off = off;
-        off += (long long)g.stride * g.ph;
-        g.bstride = (g.W + 127) & ~127;
-        g.boff = boff;
-        boff += (long long)g.bstride * g.H;
-        g.scale = scale[l];
-        g.size = (float)(int)(kPatch * scale[l]);
-        g.blur_xv = (g.W / 4) * 4;
-        g.resize_xv = resize_simd_end(g.W);
-        g.nfeat = nfeat[l];
-        // cells (src/ORBextractor.cc:778-829)
-        const float width = (float)(maxBX - minB), height = (float)(maxBY - minB);
-        const int nCols = (int)(width / 30.f), nRows = (int)(height / 30.f);
-        const int wCell = (int)ceilf(width / nCols), hCell = (int)ceilf(height / nRows);
-        if (wCell + 6 > kTile || hCell + 6 > kTile) return ORBMI_E_UNSUPPORTED;  // k_fast2's tile
-        const int cap = ((wCell + 1) / 2) * ((hCell + 1) / 2);
-        g.cell_begin = (int)cells.size();
-        g.key_base = key;
-        for (int i = 0; i < nRows; i++) {
-            const float iniY = (float)(minB + i * hCell);
-            float maxY = iniY + hCell + 6;
-            const bool skipY = iniY >= maxBY - 3;
-            if (maxY > maxBY) maxY = (float)maxBY;
-            for (int j = 0; j < nCols; j++) {
-                const float iniX = (float)(minB + j * wCell);
-                float maxX = iniX + wCell + 6;
-                CellGeom cg{};
-                cg.level = l;
-                if (!skipY && !(iniX >= maxBX - 6)) {
-                    if (maxX > maxBX) maxX = (float)maxBX;
-                    cg.x0 = (short)(int)iniX; cg.y0 = (short)(int)iniY;
-                    cg.w = (short)((int)maxX - (int)iniX); cg.h = (short)((int)maxY - (int)iniY);
-                    cg.sx = (short)(j * wCell); cg.sy = (short)(i * hCell);
-                    slot += cap;
-                    key += cap;
-                }
-                cg.roi_off = g.off + (long long)(kEdge + cg.y0) * g.stride + kEdge + cg.x0;
-                cg.stride = g.stride;
-                cg.lcell = (int)cells.size() - g.cell_begin;
-                cells.push_back(cg);
-            }
-        }
-        g.cell_end = (int)cells.size();
-        g.key_cap = key - g.key_base;
-        {   // candidate regions: region j holds the cells k % R == j of the level, sized for their caps
-            int rcap[kFastRegions] = {0}, base = g.key_base;
-            for (int k = 0; k < g.cell_end - g.cell_begin; k++)
-                if (cells[g.cell_begin + k].w) rcap[k % kFastRegions] += cap;
-            for (int j = 0; j < kFastRegions; j++) {
-                regbase[l * kFastRegions + j] = base;
-                base += rcap[j];
-            }
-            for (int k = 0; k < g.cell_end - g.cell_begin; k++)
-                cells[g.cell_begin + k].slot_base = regbase[l * kFastRegions + k % kFastRegions];
-        }
-        // order tags: cell index within the level (14 bits) << 10 | rank in the cell (< 1024)
-        if (g.key_cap > (1 << 20) || g.cell_end - g.cell_begin >= (1 << 14) || cap >= 1024) return ORBMI_E_UNSUPPORTED;
-        g.width = maxBX - minB;
-        g.height = maxBY - minB;
-        g.nIni = (int)roundf((float)g.width / (float)g.height);
-        if (g.nIni < 1) return ORBMI_E_UNSUPPORTED;  // reference indexes an empty vector here
-        g.hX = (float)g.width / g.nIni;
-        g.out_cap = std::max(g.nfeat + 3, 4 * g.nIni) + 1;
-        if (g.out_cap > kOctNodeCap || 4 * g.nIni > kOctNodeCap) return ORBMI_E_UNSUPPORTED;
-        g.out_base = outb;
-        outb += g.out_cap;
-        // resize tables (level >= 1): cv::resize INTER_LINEAR 8U coefficients
-        if (l > 0) {
-            const LevelGeom& s = levels[l - 1];
-            g.xtab_off = (int)xt.size();
-            g.ytab_off = (int)yt.size();
-            const double scale_x = 1. / ((double)g.W / s.W), scale_y = 1. / ((double)g.H / s.H);
-            int xmax = g.W;
-            std::vector<int> sxs(g.W);
-            std::vector<float> fxs(g.W);
-            for (int dx = 0; dx < g.W; dx++) {
-                float fx = (float)((dx + 0.5) * scale_x - 0.5);
-                int sx = cv_floor_f(fx);
-                fx -= sx;
-                if (sx < 0) { fx = 0; sx = 0; }
-                if (sx + 1 >= s.W) { xmax = std::min(xmax, dx); if (sx >= s.W - 1) { fx = 0; sx = s.W - 1; } }
-                sxs[dx] = sx; fxs[dx] = fx;
-            }
-            for (int dx = 0; dx < g.W; dx++) {
-                XTab e;
-                const int a0 = std::min(std::max(cv_round_host((1.f - fxs[dx]) * 2048), -32768), 32767);
-                const int a1 = std::min(std::max(cv_round_host(fxs[dx] * 2048), -32768), 32767);
-                e.sx0 = (short)sxs[dx];
-                if (dx < xmax) { e.sx1 = (short)(sxs[dx] + 1); e.a0 = (short)a0; e.a1 = (short)a1; }
-                else { e.sx1 = (short)sxs[dx]; e.a0 = 2048; e.a1 = 0; }
-                xt.push_back(e);
-            }
-            for (int dy = 0; dy < g.H; dy++) {
-                float fy = (float)((dy + 0.5) * scale_y - 0.5);
-                int sy = cv_floor_f(fy);
-                fy -= sy;
-                YTab e;
-                e.b0 = (short)std::min(std::max(cv_round_host((1.f - fy) * 2048), -32768), 32767);
-                e.b1 = (short)std::min(std::max(cv_round_host(fy * 2048), -32768), 32767);
-                e.y0 = (short)std::min(std::max(sy, 0), s.H - 1);
-                e.y1 = (short)std::min(std::max(sy + 1, 0), s.H - 1);
-                yt.push_back(e);
-            }
-        }
+    ExtractorPlan next;
+    const int rc = extractor_plan(tab, r, c, &next);
+    if (rc) return rc;
+    rows = cols = 0;
+    plan = ExtractorPlan{};
+    bcap = 0;  // the per-image buffers are sized by the plan: reserve() makes them again
+    out_capacity = 0;
+    last_batch = 0;  // the last outputs were the old geometry's
+    for (const GeomTable& t : geom_tables(next)) {
+        if (*t.dev) { (void)hipFree(*t.dev); *t.dev = nullptr; }
+        ORBMI_HIP(hipMalloc(t.dev, t.bytes ? t.bytes : 1));
+        if (t.bytes) ORBMI_HIP(hipMemcpy(*t.dev, t.host, t.bytes, hipMemcpyHostToDevice));
     }
-    // pyramid tiles: own rectangles split every level KX x KY ways; need rectangles from the top
-    // level down (need_{l-1} = own_{l-1} U the taps of need_l); level 0's need rectangle is the
-    // own one grown by the largest halo (hx, hy) of any tile.  The grid grows until a tile's LDS
-    // (parameter block, level-0 rectangle, two need rectangles) fits in 48 KB.  Each tile's
-    // parameter block: kPyrLevelWords words per level (own, need, W | H << 16, stride, offset,
-    // resize_xv, word offsets of the x / y taps), then the taps of its need rectangles.
-    {
-        int KX = 16, KY = 8;
-        for (;;) {
-            std::vector<PyrTile> tl((size_t)KX * KY * nlevels);
-            int maxarea = 0, hx = 0, hy = 0, words = 0;
-            for (int ty = 0; ty < KY; ty++)
-                for (int tx = 0; tx < KX; tx++) {
-                    PyrTile* T = &tl[((size_t)ty * KX + tx) * nlevels];
-                    for (int l = 0; l < nlevels; l++) {
-                        const LevelGeom& g = levels[l];
-                        T[l].own = PyrRect{(short)(g.W * tx / KX), (short)(g.W * (tx + 1) / KX), (short)(g.H * ty / KY),
-                                           (short)(g.H * (ty + 1) / KY)};
-                    }
-                    T[nlevels - 1].need = T[nlevels - 1].own;
-                    for (int l = nlevels - 1; l >= 1; l--) {
-                        const LevelGeom& g = levels[l];
-                        PyrRect n = T[l].need, o = T[l - 1].own, r = o;
-                        if (n.x1 > n.x0 && n.y1 > n.y0) {
-                            const XTab* X = xt.data() + g.xtab_off;
-                            const YTab* Y = yt.data() + g.ytab_off;
-                            r.x0 = std::min<short>(o.x0, X[n.x0].sx0);
-                            r.x1 = std::max<short>(o.x1, (short)(X[n.x1 - 1].sx1 + 1));
-                            r.y0 = std::min<short>(o.y0, Y[n.y0].y0);
-                            r.y1 = std::max<short>(o.y1, (short)(Y[n.y1 - 1].y1 + 1));
-                        }
-                        T[l - 1].need = r;
-                    }
-                    int w = kPyrLevelWords * nlevels;
-                    for (int l = 1; l < nlevels; l++) {
-                        const PyrRect& n = T[l].need;
-                        maxarea = std::max(maxarea, (n.x1 - n.x0) * (n.y1 - n.y0));
-                        w += 2 * (n.x1 - n.x0) + 2 * (n.y1 - n.y0);
-                    }
-                    words = std::max(words, w);
-                    hx = std::max(hx, std::max(T[0].own.x0 - T[0].need.x0, T[0].need.x1 - T[0].own.x1));
-                    hy = std::max(hy, std::max(T[0].own.y0 - T[0].need.y0, T[0].need.y1 - T[0].own.y1));
-                }
-            int area0 = 0;
-            for (int ty = 0; ty < KY; ty++)
-                for (int tx = 0; tx < KX; tx++) {
-                    const int x0 = std::max(levels[0].W * tx / KX - hx, 0), x1 = std::min(levels[0].W * (tx + 1) / KX + hx, levels[0].W);
-                    const int y0 = std::max(levels[0].H * ty / KY - hy, 0), y1 = std::min(levels[0].H * (ty + 1) / KY + hy, levels[0].H);
-                    area0 = std::max(area0, (x1 - x0) * (y1 - y0));
-                }
-            const int half = (maxarea + 15) & ~15, a0 = (area0 + 15) & ~15;
-            const int lds = 4 * words + a0 + 2 * half;
-            if (lds <= 48 * 1024 || KX * KY >= 4096) {
-                if (lds > 64 * 1024) return ORBMI_E_UNSUPPORTED;
-                pyr_blob.assign((size_t)KX * KY * words, 0u);
-                for (int t = 0; t < KX * KY; t++) {
-                    const PyrTile* T = &tl[(size_t)t * nlevels];
-                    uint32_t* B = &pyr_blob[(size_t)t * words];
-                    auto pk = [](int lo, int hi) { return (uint32_t)(uint16_t)lo | (uint32_t)(uint16_t)hi << 16; };
-                    int at = kPyrLevelWords * nlevels;
-                    for (int l = 0; l < nlevels; l++) {
-                        const LevelGeom& g = levels[l];
-                        uint32_t* G = B + l * kPyrLevelWords;
-                        G[0] = pk(T[l].own.x0, T[l].own.x1);
-                        G[1] = pk(T[l].own.y0, T[l].own.y1);
-                        G[2] = pk(T[l].need.x0, T[l].need.x1);
-                        G[3] = pk(T[l].need.y0, T[l].need.y1);
-                        G[4] = pk(g.W, g.H);
-                        G[5] = (uint32_t)g.stride;
-                        G[6] = (uint32_t)g.off;
-                        G[7] = (uint32_t)g.resize_xv;
-                        if (l == 0) continue;
-                        const XTab* X = xt.data() + g.xtab_off;
-                        const YTab* Y = yt.data() + g.ytab_off;
-                        G[8] = (uint32_t)at;
-                        for (int x = T[l].need.x0; x < T[l].need.x1; x++) {
-                            B[at++] = pk(X[x].sx0, X[x].sx1);
-                            B[at++] = pk(X[x].a0, X[x].a1);
-                        }
-                        G[9] = (uint32_t)at;
-                        for (int y = T[l].need.y0; y < T[l].need.y1; y++) {
-                            B[at++] = pk(Y[y].y0, Y[y].y1);
-                            B[at++] = pk(Y[y].b0, Y[y].b1);
-                        }
-                    }
-                }
-                pyr_kx = KX;
-                pyr_ky = KY;
-                pyr_hx = hx;
-                pyr_hy = hy;
-                pyr_blob_words = words;
-                pyr_lds_half = half;
-                pyr_lds0 = a0;
-                break;
-            }
-            if (KX <= 2 * KY) KX *= 2;
-            else KY *= 2;
-        }
-    }
-    pimg = off;
-    fast_maxw = 7; fast_maxh = 7;  // k_fast2's LDS: the largest cell ROI of the geometry
-    for (const CellGeom& cg : cells)
-        if (cg.w) { fast_maxw = std::max(fast_maxw, (int)cg.w); fast_maxh = std::max(fast_maxh, (int)cg.h); }
-    bimg = boff;
-    btiles.clear();
-    for (int l = 0; l < nlevels; l++)
-        for (int y0 = 0; y0 < levels[l].H; y0 += kBlurTH)
-            for (int x0 = 0; x0 < levels[l].W; x0 += kBlurTW) btiles.push_back(make_int2(l, x0 | (y0 << 16)));
-    nbtiles = (int)btiles.size();
-    (void)slot;
-    keys_cap = key;
-    out_cap = outb;
+    plan = std::move(next);
     rows = r; cols = c;
-    int rc;
-    if ((rc = dev_alloc(&d_levels, levels.size()))) return rc;
-    if ((rc = dev_alloc(&d_cells, cells.size()))) return rc;
-    if ((rc = dev_alloc(&d_regbase, regbase.size()))) return rc;
-    if ((rc = dev_alloc(&d_pyr_blob, pyr_blob.size()))) return rc;
-    ORBMI_HIP(hipMemcpy(d_pyr_blob, pyr_blob.data(), pyr_blob.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-    ORBMI_HIP(hipMemcpy(d_regbase, regbase.data(), regbase.size() * sizeof(int), hipMemcpyHostToDevice));
-    if ((rc = dev_alloc(&d_btiles, btiles.size()))) return rc;
-    ORBMI_HIP(hipMemcpy(d_btiles, btiles.data(), btiles.size() * sizeof(int2), hipMemcpyHostToDevice));
-    if ((rc = dev_alloc(&d_xtab, xt.size()))) return rc;
-    if ((rc = dev_alloc(&d_ytab, yt.size()))) return rc;
-    ORBMI_HIP(hipMemcpy(d_levels, levels.data(), levels.size() * sizeof(LevelGeom), hipMemcpyHostToDevice));
-    ORBMI_HIP(hipMemcpy(d_cells, cells.data(), cells.size() * sizeof(CellGeom), hipMemcpyHostToDevice));
-    if (!xt.empty()) ORBMI_HIP(hipMemcpy(d_xtab, xt.data(), xt.size() * sizeof(XTab), hipMemcpyHostToDevice));
-    if (!yt.empty()) ORBMI_HIP(hipMemcpy(d_ytab, yt.data(), yt.size() * sizeof(YTab), hipMemcpyHostToDevice));
-    bcap = 0;  // force re-reservation of per-image buffers
     return ORBMI_OK;
 }
 
+// Per-image buffers for `batch` images and internal outputs of `capacity` keypoints each.  The
+// buffers of a group share one capacity (bcap, out_capacity), which is 0 while they are made again:
+// a failure part-way leaves it 0, and the next call starts over.
 int Extractor::reserve(int batch, int capacity) {
     int rc;
+    auto regrow = [](auto** p, size_t n) { size_t cap = 0; return ensure_buf(p, &cap, n); };
+    const int nlevels = tab.nlevels;
     if (batch > bcap) {
-        if ((rc = dev_alloc(&d_pyr, (size_t)batch * pimg))) return rc;
-        if ((rc = dev_alloc(&d_blur, (size_t)batch * bimg))) return rc;
-        if ((rc = dev_alloc(&d_level_count, (size_t)batch * nlevels * kFastRegions))) return rc;
-        if ((rc = dev_alloc(&d_cand, (size_t)batch * keys_cap))) return rc;
-        if ((rc = dev_alloc(&d_node_of, (size_t)batch * keys_cap))) return rc;
-        if ((rc = dev_alloc(&d_oct, (size_t)batch * out_cap))) return rc;
-        if ((rc = dev_alloc(&d_oct_count, (size_t)batch * nlevels))) return rc;
-        if ((rc = dev_alloc(&d_counts, (size_t)batch))) return rc;
-        bcap = batch;
+        bcap = 0;
         out_capacity = 0;  // internal outputs are sized per bcap: re-reserve below
+        last_batch = 0;
+        if ((rc = regrow(&d_pyr, (size_t)batch * plan.pimg))) return rc;
+        if ((rc = regrow(&d_blur, (size_t)batch * plan.bimg))) return rc;
+        if ((rc = regrow(&d_level_count, (size_t)batch * nlevels * kFastRegions))) return rc;
+        if ((rc = regrow(&d_cand, (size_t)batch * plan.keys_cap))) return rc;
+        if ((rc = regrow(&d_node_of, (size_t)batch * plan.keys_cap))) return rc;
+        if ((rc = regrow(&d_oct, (size_t)batch * plan.out_cap))) return rc;
+        if ((rc = regrow(&d_oct_count, (size_t)batch * nlevels))) return rc;
+        if ((rc = regrow(&d_counts, (size_t)batch))) return rc;
+        bcap = batch;
     }
     if (capacity > out_capacity) {  // internal outputs (host API): bcap images x capacity
-        if ((rc = dev_alloc(&d_kps, (size_t)bcap * capacity))) return rc;
-        if ((rc = dev_alloc(&d_desc, (size_t)bcap * capacity * 32))) return rc;
+        out_capacity = 0;
+        last_batch = 0;
+        if ((rc = regrow(&d_kps, (size_t)bcap * capacity))) return rc;
+        if ((rc = regrow(&d_desc, (size_t)bcap * capacity * 32))) return rc;
         out_capacity = capacity;
     }
     return ORBMI_OK;
@@ -1774,7 +1478,10 @@ int Extractor::ensure_side_stream() {
 int Extractor::run(const uint8_t* d_images, int batch, size_t step, size_t image_stride,
                    orbmi_keypoint* kps, uint8_t* desc, int* counts, int capacity) {
     ORBMI_HIP(hipSetDevice(device));
-    const int ncells = (int)cells.size();
+    const std::vector<LevelGeom>& levels = plan.levels;
+    const int nlevels = tab.nlevels, ncells = (int)plan.cells.size(), nbtiles = (int)plan.btiles.size();
+    const int fast_maxw = plan.fast_maxw, fast_maxh = plan.fast_maxh, keys_cap = plan.keys_cap, out_cap = plan.out_cap;
+    const long long pimg = plan.pimg, bimg = plan.bimg;
     // GaussianBlur needs only the pyramid.  Small batches (<= kFuseBlurMaxOctrees octrees): it rides
     // in the octree launch as extra workgroups on the CUs the octrees leave idle (a side stream's
     // event round trip costs more there: 7.8k vs 6.9k stereo frames/s).  Large batches: it runs on
@@ -1804,10 +1511,10 @@ int Extractor::run(const uint8_t* d_images, int batch, size_t step, size_t image
         }
     } else {
         hipEvent_t ev = prof_begin(ORBMI_STAGE_PYR_LEVEL0);  // the whole pyramid
-        hipLaunchKernelGGL(k_pyramid, dim3(pyr_kx * pyr_ky, 1, batch), dim3(kPyrThreads),
-                           4 * pyr_blob_words + pyr_lds0 + 2 * pyr_lds_half, stream, d_images, step, image_stride, d_pyr,
-                           pimg, d_pyr_blob, pyr_blob_words, nlevels, pyr_kx, pyr_ky, levels[0].W, levels[0].H, pyr_hx,
-                           pyr_hy, d_level_count, pyr_lds0, pyr_lds_half);
+        hipLaunchKernelGGL(k_pyramid, dim3(plan.kx * plan.ky, 1, batch), dim3(kPyrThreads),
+                           4 * plan.blob_words + plan.lds0 + 2 * plan.lds_half, stream, d_images, step, image_stride, d_pyr,
+                           pimg, d_pyr_blob, plan.blob_words, nlevels, plan.kx, plan.ky, levels[0].W, levels[0].H, plan.hx,
+                           plan.hy, d_level_count, plan.lds0, plan.lds_half);
         prof_end(ORBMI_STAGE_PYR_LEVEL0, ev);
     }
     if (blur_mode == 0) {  // side: the blur on the side stream from this point of the stream
@@ -1914,18 +1621,14 @@ __global__ __launch_bounds__(256) void k_copy_host(const uint8_t* __restrict__ s
 }
 
 int Extractor::upload_host(const uint8_t* h_images, size_t bytes, const uint8_t** d_out) {
-    if (bytes > image_bytes) {
-        if (d_image) (void)hipFree(d_image);
-        d_image = nullptr;
-        image_bytes = 0;
-        ORBMI_HIP(hipMalloc((void**)&d_image, bytes));
-        image_bytes = bytes;
-    }
+    const int rc = ensure_buf(&d_image, &image_bytes, bytes);
+    if (rc) return rc;
     hipPointerAttribute_t at;
     bool pinned = false;
     if (hipPointerGetAttributes(&at, h_images) == hipSuccess) pinned = at.type == hipMemoryTypeHost;
     else (void)hipGetLastError();
     const uint8_t* src = h_images;
+    hipEvent_t staged = nullptr;
     if (!pinned) {  // pageable: one host copy into a pinned staging buffer of the handle (two, alternating)
         const int k = stage_next;
         stage_next ^= 1;
@@ -1941,15 +1644,12 @@ int Extractor::upload_host(const uint8_t* h_images, size_t bytes, const uint8_t*
         else ORBMI_HIP(hipEventSynchronize(stage_ev[k]));  // its last copy kernel has read it
         std::memcpy(h_stage[k], h_images, bytes);
         src = h_stage[k];
-        const int blocks = (int)std::min<size_t>(1024, (bytes / 16 + 255) / 256 + 1);
-        hipLaunchKernelGGL(k_copy_host, dim3(blocks), dim3(256), 0, stream, src, d_image, bytes);
-        ORBMI_HIP(hipGetLastError());
-        ORBMI_HIP(hipEventRecord(stage_ev[k], stream));
-    } else {
-        const int blocks = (int)std::min<size_t>(1024, (bytes / 16 + 255) / 256 + 1);
-        hipLaunchKernelGGL(k_copy_host, dim3(blocks), dim3(256), 0, stream, src, d_image, bytes);
-        ORBMI_HIP(hipGetLastError());
+        staged = stage_ev[k];
     }
+    const int blocks = (int)std::min<size_t>(1024, (bytes / 16 + 255) / 256 + 1);
+    hipLaunchKernelGGL(k_copy_host, dim3(blocks), dim3(256), 0, stream, src, d_image, bytes);
+    ORBMI_HIP(hipGetLastError());
+    if (staged) ORBMI_HIP(hipEventRecord(staged, stream));  // the staging buffer is free again after the copy
     *d_out = d_image;
     return ORBMI_OK;
 }
@@ -1967,9 +1667,10 @@ void Extractor::release() {
     prof_pending.clear();
     prof_pool.clear();
     if (device >= 0) (void)hipSetDevice(device);
-    void* ptrs[] = {d_levels, d_cells, d_regbase, d_pyr_blob, d_btiles, d_blur, d_xtab, d_ytab, d_pyr, d_level_count, d_cand, d_node_of,
-                    d_oct, d_oct_count, d_kps, d_desc, d_counts, d_image, d_scale_tab, d_row_start,
-                    d_row_list, d_sad, d_stereo_u, d_stereo_d};
+    for (const GeomTable& t : geom_tables(plan))
+        if (*t.dev) (void)hipFree(*t.dev);
+    void* ptrs[] = {d_blur, d_pyr, d_level_count, d_cand, d_node_of, d_oct, d_oct_count, d_kps, d_desc, d_counts,
+                    d_image, d_scale_tab, d_row_start, d_row_list, d_sad, d_stereo_u, d_stereo_d};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     if (stream) (void)hipStreamDestroy(stream);

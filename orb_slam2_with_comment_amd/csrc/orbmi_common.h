@@ -9,6 +9,7 @@
 #include <string.h>
 
 #include "../../include/orbmi.h"
+#include "extractor_plan.h"  // kEdge, kHalfPatch, kPatch, kMaxLevels, reflect101, cv_floor_f, cv_round_f
 #include "wave_ops.h"
 
 #define ORBMI_HIP(call)                                                                 \
@@ -23,26 +24,7 @@
 
 namespace orbmi {
 
-constexpr int kEdge = 19;        // EDGE_THRESHOLD  src/ORBextractor.cc:74
-constexpr int kHalfPatch = 15;   // HALF_PATCH_SIZE src/ORBextractor.cc:73
-constexpr int kPatch = 31;       // PATCH_SIZE      src/ORBextractor.cc:72
-constexpr int kMaxLevels = 16;
 constexpr int kWave = 64;
-
-__host__ __device__ inline int reflect101(int p, int len) {
-    if ((unsigned)p < (unsigned)len) return p;
-    if (len == 1) return 0;
-    do {
-        if (p < 0) p = -p;
-        else p = 2 * len - 2 - p;
-    } while ((unsigned)p >= (unsigned)len);
-    return p;
-}
-
-__host__ __device__ inline int cv_floor_f(float v) { int i = (int)v; return i - (i > v); }
-
-// cvRound(float): round-half-even (v_rndne_f32 on device, rint under the default mode on host)
-__host__ __device__ inline int cv_round_f(float v) { return (int)__builtin_rintf(v); }
 
 __device__ inline int popc256(const uint4& a0, const uint4& a1, const uint4& b0, const uint4& b1) {
     return __popc(a0.x ^ b0.x) + __popc(a0.y ^ b0.y) + __popc(a0.z ^ b0.z) + __popc(a0.w ^ b0.w) +

@@ -266,12 +266,12 @@ __global__ __launch_bounds__(1024) void k_stereo_filter(const int* __restrict__ 
 int stereo_run(Extractor& Lx, int itemL, Extractor& Rx, int itemR, float bf, float fx, float* d_u,
                float* d_depth, int cap) {
     ORBMI_HIP(hipSetDevice(Lx.device));
-    const int nrows = Lx.levels[0].H;
+    const int nrows = Lx.plan.levels[0].H;
     if (nrows + 1 > kStereoRowsMax) return ORBMI_E_UNSUPPORTED;
     const int capR = Rx.last_capacity, capL = Lx.last_capacity;
     // a right keypoint enters rows floor(y - r) .. ceil(y + r), r = 2 * scale[octave]: at most
     // ceil(4 * scale) + 2 of them (and never more than the image has), so the list cannot overfill
-    const float smax = *std::max_element(Lx.scale.begin(), Lx.scale.end());
+    const float smax = *std::max_element(Lx.tab.scale.begin(), Lx.tab.scale.end());
     const int list_cap = capR * std::min((int)std::ceil(4.0f * smax) + 2, nrows);
     int rc;
     if ((rc = ensure_buf(&Lx.d_row_start, &Lx.row_cap, (size_t)nrows + 1))) return rc;
@@ -288,11 +288,11 @@ int stereo_run(Extractor& Lx, int itemL, Extractor& Rx, int itemR, float bf, flo
     a.countL = Lx.last_counts + itemL;
     a.kpsR = kpsR;
     a.descR = Rx.last_desc + (long long)itemR * capR * 32;
-    a.pyrL = Lx.d_pyr + (long long)itemL * Lx.pimg;
-    a.pyrR = Rx.d_pyr + (long long)itemR * Rx.pimg;
+    a.pyrL = Lx.d_pyr + (long long)itemL * Lx.plan.pimg;
+    a.pyrR = Rx.d_pyr + (long long)itemR * Rx.plan.pimg;
     a.levels = Lx.d_levels;
     a.scale = Lx.d_scale_tab;
-    a.inv_scale = Lx.d_scale_tab + Lx.nlevels;
+    a.inv_scale = Lx.d_scale_tab + Lx.tab.nlevels;
     a.row_start = Lx.d_row_start;
     a.row_list = Lx.d_row_list;
     a.u_right = d_u;

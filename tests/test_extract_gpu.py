@@ -362,3 +362,69 @@ def test_batch_host_images_levelwise(orb, oracle, images):
             assert counts[j] == len(k_ref)
             np.testing.assert_array_equal(kk[j, :counts[j]].view(_capi.KP_DTYPE).reshape(-1), k_ref)
             np.testing.assert_array_equal(dd[j, :counts[j]], d_ref)
+
+
+def test_refused_size_leaves_the_handle_intact(orb, oracle):
+    """A size the extractor refuses (70 x 128 at two levels: level 0 fits, level 1 does not) between
+    accepted ones on one handle: the refusal must leave the handle's geometry as it was -- the next
+    call at the earlier size takes set_geometry's early-out and runs on it -- and a change of size
+    after it must plan afresh.  First through orbmi_extract, then through
+    orbmi_extract_batch_device with batches of 9 (the level-by-level pyramid)."""
+    import ctypes as C
+    import torch
+    from orb_slam2_with_comment_amd import _capi
+    p = oracle.params(300, 1.2, 2, 20, 7)
+    ex = _extractor(orb, p)
+    rng = np.random.default_rng(5)
+    B = 9
+    first, refused, other = (rng.integers(0, 256, (B, r, c), dtype=np.uint8) for r, c in ((96, 128), (70, 128), (97, 131)))
+    ref_pyr = [oracle.pyramid(p, first[i]) for i in range(B)]
+
+    def levels_are_the_first(item):
+        for l in range(p.nlevels):
+            np.testing.assert_array_equal(ex.pyramid_level(l, padded=True, item=item), ref_pyr[item][l])
+
+    def host(img):
+        k, d = ex(img)
+        _assert_same(oracle, p, ex, img, k, d)
+
+    host(first[0])
+    with pytest.raises(_capi.OrbmiError) as e:
+        ex(refused[0])
+    assert e.value.code == _capi.ORBMI_E_UNSUPPORTED
+    levels_are_the_first(0)
+    host(first[0])
+    host(other[0])
+    host(first[0])
+
+    cap = p.nfeatures + 64
+    d_k = torch.zeros((B, cap, 7), dtype=torch.int32, device="cuda")
+    d_d = torch.zeros((B, cap, 32), dtype=torch.uint8, device="cuda")
+    d_n = torch.zeros(B, dtype=torch.int32, device="cuda")
+
+    def batch(imgs):
+        _, r, c = imgs.shape
+        d_img = torch.from_numpy(imgs).cuda()
+        torch.cuda.synchronize()
+        rc = _capi.lib().orbmi_extract_batch_device(
+            ex.handle, C.c_void_p(d_img.data_ptr()), B, r, c, c, r * c, C.c_void_p(d_k.data_ptr()),
+            C.c_void_p(d_d.data_ptr()), C.c_void_p(d_n.data_ptr()), cap)
+        if rc:
+            return rc
+        _capi.check("sync", _capi.lib().orbmi_extractor_synchronize(ex.handle))
+        counts, kk, dd = d_n.cpu().numpy(), d_k.cpu().numpy(), d_d.cpu().numpy()
+        for i in range(B):
+            k_ref, d_ref = oracle.extract(p, imgs[i])
+            assert counts[i] == len(k_ref), i
+            np.testing.assert_array_equal(kk[i, :counts[i]].view(_capi.KP_DTYPE).reshape(-1), k_ref, err_msg=str(i))
+            np.testing.assert_array_equal(dd[i, :counts[i]], d_ref, err_msg=str(i))
+        return 0
+
+    assert batch(first) == 0
+    assert batch(refused) == _capi.ORBMI_E_UNSUPPORTED
+    levels_are_the_first(0)
+    levels_are_the_first(B - 1)
+    assert batch(first) == 0
+    assert batch(other) == 0
+    assert batch(first) == 0
+    ex.close()
