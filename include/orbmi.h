@@ -156,6 +156,53 @@ int orbmi_compute_stereo_from_rgbd_keys(int device, const orbmi_keypoint* keys, 
 int orbmi_cvt_gray(int device, const uint8_t* image, size_t image_step, int channels, int rgb, int rows, int cols,
                    uint8_t* gray, size_t gray_step);
 
+/* ---- Stereo rectification: cv::initUndistortRectifyMap + cv::remap ------------------------ */
+
+/* One camera of a rig that is not factory-rectified, as the settings file gives it
+ * (Examples/Stereo/stereo_euroc.cc:55-90: LEFT/RIGHT.K, .D, .R, .P, .height, .width), row-major
+ * doubles.  D = k1 k2 p1 p2 [k3 [k4 k5 k6]] with nd = 4, 5 or 8 (thin-prism and tilt terms are
+ * not built: any other nd is ORBMI_E_ARG).  rows x cols is the size of the rectified image. */
+typedef struct orbmi_rectify_camera {
+    double K[9];
+    double D[8];
+    int nd;
+    double R[9];
+    double P[12];
+    int rows, cols;
+} orbmi_rectify_camera;
+
+/* cv::initUndistortRectifyMap(K, D, R, P.rowRange(0,3).colRange(0,3), Size(cols, rows), CV_32F,
+ * map1, map2) (stereo_euroc.cc:92-93) restated from OpenCV 3.x's documented algorithm in fp64
+ * (DESIGN.md 6r).  map1 / map2: rows x cols host floats, contiguous.  Host only, no GPU. */
+int orbmi_init_undistort_rectify_map(const orbmi_rectify_camera* camera, float* map1, float* map2);
+
+typedef struct orbmi_rectifier orbmi_rectifier;
+
+/* The maps of one camera on `device`, converted once into cv::remap's fixed-point form
+ * (coordinates rounded half-even to 1/32 pixel; a NaN or a coordinate beyond int32 range reads as
+ * outside the source).  map1 / map2: rows x cols host floats, contiguous -- from
+ * orbmi_init_undistort_rectify_map or any other source (they are not kept). */
+int orbmi_rectifier_create(int device, const float* map1, const float* map2, int rows, int cols,
+                           orbmi_rectifier** out);
+void orbmi_rectifier_destroy(orbmi_rectifier* h);
+
+/* cv::remap(src, dst, map1, map2, cv::INTER_LINEAR) (stereo_euroc.cc:122-123; BORDER_CONSTANT 0)
+ * for 8-bit single-channel images: dst has the maps' size, src its own (at most 32767 in either
+ * dimension, ORBMI_E_ARG beyond); pitches in bytes.  src / dst: host or device memory of the
+ * handle's device (detected per call).  stream: a hipStream_t of the caller or NULL.  With a
+ * stream the inputs are read after the work enqueued on it so far and the stream waits for the
+ * outputs, and a call whose pointers are all device memory does not block; with NULL the outputs
+ * are complete on return, and device inputs must be complete on entry: the handle's stream is
+ * non-blocking and waits for no other stream, the legacy default stream included (synchronise
+ * it first, as rectify.py does).  A refused call leaves the handle as it was. */
+int orbmi_remap(orbmi_rectifier* h, const uint8_t* src, int src_rows, int src_cols, size_t src_step, uint8_t* dst,
+                size_t dst_step, void* stream);
+/* Both images of a pair in one launch (on the left handle's stream; both handles on one device).
+ * The sources share a size and a pitch, the destinations a pitch; each has its handle's size. */
+int orbmi_remap_pair(orbmi_rectifier* left, orbmi_rectifier* right, const uint8_t* src_left, const uint8_t* src_right,
+                     int src_rows, int src_cols, size_t src_step, uint8_t* dst_left, uint8_t* dst_right, size_t dst_step,
+                     void* stream);
+
 /* ---- ORBmatcher ----------------------------------------------------------------------- */
 
 /* Read-only view of the Frame members the matchers use (include/Frame.h).  Pointers may be
@@ -886,6 +933,17 @@ int orbmi_slam_track_stereo(orbmi_slam* h, const uint8_t* left, const uint8_t* r
 int orbmi_slam_track_stereo_ahead(orbmi_slam* h, const uint8_t* left, const uint8_t* right, int rows, int cols,
                                   size_t step, double timestamp, const uint8_t* next_left,
                                   const uint8_t* next_right, float* tcw_out, int* has_pose);
+
+/* orbmi_slam_create for a rig whose images are not rectified (Examples/Stereo/stereo_euroc.cc:
+ * 55-137): both maps are built once, and orbmi_slam_track_stereo / _ahead then take the raw
+ * images -- each pair is uploaded, remapped on the device (one launch) into the buffer the
+ * extractor reads, and the Frame constructor continues as on a plain handle.  Both cameras'
+ * sizes must equal s->width x s->height (ORBMI_E_ARG and no handle otherwise); a frame of
+ * another size returns ORBMI_E_ARG and leaves the handle usable.  s describes the rectified
+ * rig (Camera.fx ... = LEFT.P). */
+int orbmi_slam_create_stereo_rectify(const orbmi_slam_settings* s, const orbmi_rectify_camera* left_cam,
+                                     const orbmi_rectify_camera* right_cam, int device,
+                                     orbmi_vocabulary* vocabulary, orbmi_slam** out);
 
 /* System(strSettingsFile, RGBD): what Tracking reads for an RGB-D sensor beyond
  * orbmi_slam_settings -- mDistCoef (ndist = 4 or 5), mDepthMapFactor already inverted

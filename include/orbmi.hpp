@@ -798,6 +798,49 @@ private:
     orbmi_slam* h_ = nullptr;
 };
 
+// What Examples/Stereo/stereo_euroc.cc:92-93, 122-123 does with cv::initUndistortRectifyMap and
+// cv::remap: both cameras' maps built once (left / right = LEFT / RIGHT.K, .D, .R, .P and the size
+// from the settings file), then each raw pair remapped in one launch.  Images are 8-bit gray,
+// host or device memory; the rectified images have the cameras' sizes.
+class StereoRectifier {
+public:
+    StereoRectifier(const orbmi_rectify_camera& left, const orbmi_rectify_camera& right, int device = 0) {
+        try {
+            create(left, &l_, device);
+            create(right, &r_, device);
+        } catch (...) {
+            orbmi_rectifier_destroy(l_);
+            throw;
+        }
+    }
+    ~StereoRectifier() {
+        orbmi_rectifier_destroy(l_);
+        orbmi_rectifier_destroy(r_);
+    }
+    StereoRectifier(const StereoRectifier&) = delete;
+    StereoRectifier& operator=(const StereoRectifier&) = delete;
+
+    // cv::remap(imLeft, imLeftRect, M1l, M2l, cv::INTER_LINEAR); cv::remap(imRight, imRightRect, M1r, M2r, ...)
+    void operator()(const uint8_t* imLeft, const uint8_t* imRight, int rows, int cols, size_t step, uint8_t* imLeftRect,
+                    uint8_t* imRightRect, size_t rectStep, void* stream = nullptr) {
+        check(orbmi_remap_pair(l_, r_, imLeft, imRight, rows, cols, step, imLeftRect, imRightRect, rectStep, stream),
+              "orbmi_remap_pair");
+    }
+
+    orbmi_rectifier* left() const { return l_; }
+    orbmi_rectifier* right() const { return r_; }
+
+private:
+    static void create(const orbmi_rectify_camera& c, orbmi_rectifier** out, int device) {
+        if (c.rows <= 0 || c.cols <= 0) throw Error(ORBMI_E_ARG, "StereoRectifier");
+        std::vector<float> m1((size_t)c.rows * c.cols), m2(m1.size());
+        check(orbmi_init_undistort_rectify_map(&c, m1.data(), m2.data()), "orbmi_init_undistort_rectify_map");
+        check(orbmi_rectifier_create(device, m1.data(), m2.data(), c.rows, c.cols, out), "orbmi_rectifier_create");
+    }
+    orbmi_rectifier* l_ = nullptr;
+    orbmi_rectifier* r_ = nullptr;
+};
+
 }  // namespace orbmi
 
 #endif  // ORBMI_HPP

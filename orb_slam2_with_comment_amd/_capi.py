@@ -127,6 +127,12 @@ _PROTOS = {
     "orbmi_compute_stereo_from_rgbd": (_i, [_vp, _i, _vp, _i, _sz, _f, _i, _i, _vp, _f, _vp, _vp, _vp, _i]),
     "orbmi_compute_stereo_from_rgbd_keys": (_i, [_i, _vp, _i, _vp, _i, _sz, _f, _i, _i, _vp, _f, _vp, _vp, _vp]),
     "orbmi_cvt_gray": (_i, [_i, _vp, _sz, _i, _i, _i, _i, _vp, _sz]),
+    "orbmi_init_undistort_rectify_map": (_i, [_vp, _vp, _vp]),
+    "orbmi_rectifier_create": (_i, [_i, _vp, _vp, _i, _i, C.POINTER(_vp)]),
+    "orbmi_rectifier_destroy": (None, [_vp]),
+    "orbmi_remap": (_i, [_vp, _vp, _i, _i, _sz, _vp, _sz, _vp]),
+    "orbmi_remap_pair": (_i, [_vp, _vp, _vp, _vp, _i, _i, _sz, _vp, _vp, _sz, _vp]),
+    "orbmi_slam_create_stereo_rectify": (_i, [_vp, _vp, _vp, _i, _vp, C.POINTER(_vp)]),
     "orbmi_slam_create_rgbd": (_i, [_vp, _vp, _i, _vp, C.POINTER(_vp)]),
     "orbmi_slam_track_rgbd": (_i, [_vp, _vp, _i, _sz, _vp, _i, _sz, _i, _i, C.c_double, _vp, C.POINTER(_i)]),
     "orbmi_sim3_ransac_batch": (_i, [_vp, _i, _vp, _vp]),

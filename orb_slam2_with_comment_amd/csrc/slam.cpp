@@ -168,6 +168,35 @@ int orbmi_slam_create_rgbd(const orbmi_slam_settings* s, const orbmi_rgbd_settin
     return slam_create(s, r, device, vocabulary, out);
 }
 
+int orbmi_slam_create_stereo_rectify(const orbmi_slam_settings* s, const orbmi_rectify_camera* left_cam,
+                                     const orbmi_rectify_camera* right_cam, int device, orbmi_vocabulary* vocabulary,
+                                     orbmi_slam** out) {
+    if (!out) return ORBMI_E_ARG;
+    *out = nullptr;
+    const orbmi_rectify_camera* cams[2] = {left_cam, right_cam};
+    for (const orbmi_rectify_camera* c : cams)
+        if (!s || !orbmi::rectify::camera_ok(c) || c->cols != s->width || c->rows != s->height ||
+            c->rows > orbmi::rectify::kMaxSource || c->cols > orbmi::rectify::kMaxSource)
+            return ORBMI_E_ARG;
+    orbmi_slam* h = nullptr;
+    int rc = slam_create(s, nullptr, device, vocabulary, &h);
+    if (rc) return rc;
+    // initUndistortRectifyMap of both cameras, once (Examples/Stereo/stereo_euroc.cc:92-93)
+    std::vector<float> m1((size_t)s->width * s->height), m2(m1.size());
+    if (hipSetDevice(device) != hipSuccess) rc = ORBMI_E_HIP;
+    for (int e = 0; e < 2 && !rc; e++) {
+        rc = orbmi_init_undistort_rectify_map(cams[e], m1.data(), m2.data());
+        if (!rc) rc = h->rect[e].upload(m1.data(), m2.data(), s->height, s->width);
+    }
+    if (rc) {
+        orbmi_slam_destroy(h);
+        return rc;
+    }
+    h->rectify = true;
+    *out = h;
+    return ORBMI_OK;
+}
+
 int orbmi_slam_wait_local_mapping(orbmi_slam* h) {
     if (!h) return ORBMI_E_ARG;
     return h->wait_local_mapping();
@@ -187,6 +216,7 @@ void orbmi_slam_destroy(orbmi_slam* h) {
     if (h->tstream) (void)hipStreamSynchronize(h->tstream);
     h->hold_report();
     h->free_dev();
+    for (orbmi::RectifyTable& t : h->rect) t.release();
     h->free_track_buffers();
     orbmi_ba_destroy(h->ba);
     orbmi_pose_destroy(h->pose);
@@ -233,6 +263,8 @@ static int track_stereo(orbmi_slam* h, const uint8_t* left, const uint8_t* right
                         int* has_pose) {
     if (!h || !left || !right || rows <= 0 || cols <= 0 || step < (size_t)cols) return ORBMI_E_ARG;
     if (h->rgbd) return ORBMI_E_STATE;
+    // the record tables are the cameras' size: another frame is refused before anything is touched
+    if (h->rectify && (rows != h->rect[0].rows || cols != h->rect[0].cols)) return ORBMI_E_ARG;
     if (h->reset_pending) SLAM_CHECK(h->deferred_reset());  // (src/System.cc:139-146)
     TrackedFrame cf;
     cf.id = h->frame_count;

@@ -41,6 +41,7 @@
 #include <hip/hip_runtime_api.h>
 
 #include "../../include/orbmi_debug.h"
+#include "rectifier.h"
 #include "rgbd.h"
 #include "slam_map.h"
 #include "tri_geom.h"
@@ -121,6 +122,10 @@ struct orbmi_slam : Map {
     bool rgbd = false;
     orbmi_rgbd_settings rs{};
     orbmi::UndistortCam ucam{};
+    // orbmi_slam_create_stereo_rectify: TrackStereo takes raw images, frame_enqueue remaps them
+    // with the left and right record tables before the extraction
+    bool rectify = false;
+    orbmi::RectifyTable rect[2];
     // mnMinX, mnMaxX, mnMinY, mnMaxY (Frame::ComputeImageBounds, src/Frame.cc:471-499), computed
     // once at creation as the reference does for its first Frame (mbInitialComputations)
     float bounds[4] = {0.f, 0.f, 0.f, 0.f};

@@ -133,13 +133,24 @@ int orbmi_slam::read_back(int k, int counts) {
 int orbmi_slam::frame_enqueue(const uint8_t* L, const uint8_t* R, int rows, int cols, size_t step, int k) {
     if (k < 0 || k >= kSlots) return ORBMI_E_ARG;
     const size_t img = (size_t)rows * cols;
-    SLAM_CHECK(image_buffers(2 * img));
+    // a rectifying handle stages the raw pair behind the pair the extractor reads (image_buffers
+    // sizes the pinned mirror like the device buffer: of the mirror only the first 2 * img bytes
+    // are used, the raw pair's)
+    const size_t raw = rectify ? 2 * img : 0;
+    SLAM_CHECK(image_buffers(raw + 2 * img));
     SLAM_CHECK(ensure_slots());
     for (int r = 0; r < rows; r++) {
         std::memcpy(dev.h_img + (size_t)r * cols, L + (size_t)r * step, cols);
         std::memcpy(dev.h_img + img + (size_t)r * cols, R + (size_t)r * step, cols);
     }
-    if (hipMemcpyAsync(dev.img, dev.h_img, 2 * img, hipMemcpyHostToDevice, xstream) != hipSuccess) return ORBMI_E_HIP;
+    if (hipMemcpyAsync(dev.img + raw, dev.h_img, 2 * img, hipMemcpyHostToDevice, xstream) != hipSuccess) return ORBMI_E_HIP;
+    if (rectify) {  // cv::remap of both images (Examples/Stereo/stereo_euroc.cc:122-123), one launch
+        orbmi::RemapImage im[2];
+        for (int e = 0; e < 2; e++)
+            im[e] = orbmi::RemapImage{rect[e].d_rec, dev.img + raw + e * img, dev.img + e * img, rows, cols, rows, cols,
+                                      (unsigned)cols, (unsigned)cols};
+        SLAM_CHECK(orbmi::remap_run(xstream, im, 2));
+    }
     const int cap = dev.cap;
     SLAM_CHECK(orbmi_extract_batch_device(left, dev.img, 2, rows, cols, cols, img, dev.kps[k], dev.desc[k], dev.cnt[k],
                                           cap));

@@ -41,9 +41,12 @@ class NativeStereoSLAM:
     one dict per frame with the counters the stage that ran produced."""
 
     def __init__(self, settings, device: int = 0, vocabulary=None, local_ba: bool = True, local_mapping: bool = True,
-                 async_local_mapping: bool = False, record: bool = False, sensor: str = "stereo"):
+                 async_local_mapping: bool = False, record: bool = False, sensor: str = "stereo",
+                 rectify: bool = False):
         """sensor: "stereo" (TrackStereo) or "rgbd" (TrackRGBD, orbmi_slam_create_rgbd: the settings'
-        distortion coefficients, DepthMapFactor and Camera.RGB).  record: keep the schedule, the LocalBA log and the per-keyframe state log
+        distortion coefficients, DepthMapFactor and Camera.RGB).  rectify (stereo only): TrackStereo
+        takes raw images and rectifies them on the device with the settings' LEFT / RIGHT parameters
+        (orbmi_slam_create_stereo_rectify; stereo_euroc.cc's initUndistortRectifyMap + remap).  record: keep the schedule, the LocalBA log and the per-keyframe state log
         (orbmi_slam_set_recording) for schedule(), local_ba_log() and keyframe_state_log()."""
         from .settings import Settings, load_settings
         s = settings if isinstance(settings, Settings) else load_settings(settings)
@@ -61,6 +64,8 @@ class NativeStereoSLAM:
         h = C.c_void_p()
         if sensor not in ("stereo", "rgbd"):
             raise ValueError("sensor is 'stereo' or 'rgbd'")
+        if rectify and sensor != "stereo":
+            raise ValueError("rectify applies to the stereo sensor")
         self.sensor = sensor
         if sensor == "rgbd":
             r = RgbdSettings()
@@ -70,6 +75,14 @@ class NativeStereoSLAM:
             r.ndist, r.depth_map_factor, r.rgb = len(d), float(s.depth_map_factor), int(bool(s.rgb))
             check("orbmi_slam_create_rgbd", lib().orbmi_slam_create_rgbd(
                 C.addressof(c), C.addressof(r), device, self._voc._h if self._voc else None, C.byref(h)))
+        elif rectify:
+            from .rectify import camera_struct
+            if s.rectification is None:
+                raise ValueError("rectify=True needs the settings' LEFT / RIGHT rectification parameters")
+            cl, cr = (camera_struct(cam) for cam in s.rectification)
+            check("orbmi_slam_create_stereo_rectify", lib().orbmi_slam_create_stereo_rectify(
+                C.addressof(c), C.addressof(cl), C.addressof(cr), device, self._voc._h if self._voc else None,
+                C.byref(h)))
         else:
             check("orbmi_slam_create", lib().orbmi_slam_create(C.addressof(c), device,
                                                                self._voc._h if self._voc else None, C.byref(h)))

@@ -10,6 +10,7 @@ float32 arithmetic of the Tracking constructor.
 from __future__ import annotations
 
 import dataclasses
+import functools
 import re
 
 import numpy as np
@@ -77,6 +78,42 @@ def _f32(x) -> np.float32:
     return np.float32(x if isinstance(x, (int, float, np.floating, np.integer)) else 0.0)
 
 
+@dataclasses.dataclass(frozen=True)
+class RectifyCamera:
+    """One camera of a rig that is not factory-rectified: LEFT / RIGHT .K, .D, .R, .P and the
+    size (Examples/Stereo/stereo_euroc.cc:55-90), float64 as the file has them."""
+    K: np.ndarray   # 3 x 3
+    D: np.ndarray   # k1 k2 p1 p2 [k3 [k4 k5 k6]]
+    R: np.ndarray   # 3 x 3
+    P: np.ndarray   # 3 x 4
+    rows: int
+    cols: int
+
+
+_RECTIFY_KEYS = ("K", "D", "R", "P", "width", "height")
+
+
+def _rectification(fs: dict):
+    """(left, right) RectifyCamera when the file has every LEFT / RIGHT key, None when it has
+    none of them; some but not all is the reference's "Calibration parameters to rectify stereo
+    are missing!" (stereo_euroc.cc:85-90)."""
+    names = [f"{side}.{k}" for side in ("LEFT", "RIGHT") for k in _RECTIFY_KEYS]
+    have = [n for n in names if n in fs]
+    if not have:
+        return None
+    if len(have) != len(names):
+        missing = ", ".join(n for n in names if n not in fs)
+        raise ValueError(f"Calibration parameters to rectify stereo are missing! ({missing})")
+    cams = []
+    for side in ("LEFT", "RIGHT"):
+        K, D, R, P = (np.asarray(fs[f"{side}.{k}"], np.float64) for k in "KDRP")
+        rows, cols = int(fs[f"{side}.height"]), int(fs[f"{side}.width"])
+        if K.shape != (3, 3) or R.shape != (3, 3) or P.shape != (3, 4) or rows <= 0 or cols <= 0:
+            raise ValueError(f"Calibration parameters to rectify stereo are missing! ({side}: bad shape)")
+        cams.append(RectifyCamera(K, D.ravel(), R, P, rows, cols))
+    return tuple(cams)
+
+
 @dataclasses.dataclass
 class Settings:
     """The Tracking constructor's view of a settings file (src/Tracking.cc:53-143)."""
@@ -101,6 +138,15 @@ class Settings:
     width: int               # Camera.width / height (read by the examples, not by Tracking)
     height: int
     raw: dict
+
+    @functools.cached_property
+    def rectification(self):
+        """(left, right) RectifyCamera of a rig whose images are to be rectified, from the file's
+        LEFT / RIGHT keys; None when it has none of them (KITTI, TUM).  Raises ValueError when
+        only some are there, as stereo_euroc.cc stops with "Calibration parameters to rectify
+        stereo are missing!" -- on first access, so a file read for Tracking's values alone still loads.
+        Parsed once per Settings object (dataclasses.replace makes a new one)."""
+        return _rectification(self.raw)
 
     @property
     def camera(self):

@@ -157,6 +157,27 @@ def _undistorted_rays(cam) -> np.ndarray:
     return np.stack([x, y, np.ones_like(x)], -1)
 
 
+def _cast_room(dw: np.ndarray, o: np.ndarray):
+    """(image before noise, ray parameter t of the nearest hit) of rays o + t dw in _ROOM."""
+    best_t = np.full(dw.shape[:2], np.inf)
+    img = np.zeros(dw.shape[:2])
+    for pid, (axis, off) in enumerate(_ROOM):
+        with np.errstate(divide="ignore", invalid="ignore"):
+            t = (off - o[axis]) / dw[..., axis]
+        hit = (t > 0) & (t < best_t)
+        if not hit.any():
+            continue
+        p = (o + dw[hit] * t[hit][:, None]) / _ROOM_TEXTURE_SCALE
+        ax = [k for k in range(3) if k != axis]
+        a, b = p[:, ax[0]], p[:, ax[1]]
+        val = 128.0 + 50.0 * np.sin(0.11 * a + pid) * np.cos(0.07 * b)
+        val += 80.0 * (_hash01(np.floor(a / 0.6), np.floor(b / 0.6), 11 + pid) - 0.5)
+        val += 50.0 * (_hash01(np.floor(a / 0.17), np.floor(b / 0.17), 23 + pid) - 0.5)
+        img[hit] = val
+        best_t[hit] = t[hit]
+    return img, best_t
+
+
 def rgbd_frame(cam: RGBDCamera, frame: int, seed_base: int = 9000, noise: float = 4.0):
     """(rgb u8 H x W x 3, depth u16 H x W, Twc) of frame `frame` of the TUM-shaped sequence.
 
@@ -173,22 +194,7 @@ def rgbd_frame(cam: RGBDCamera, frame: int, seed_base: int = 9000, noise: float 
     dc = _undistorted_rays(cam)
     dw = dc @ Twc[:3, :3].T
     o = Twc[:3, 3]
-    best_t = np.full(dc.shape[:2], np.inf)
-    img = np.zeros(dc.shape[:2])
-    for pid, (axis, off) in enumerate(_ROOM):
-        with np.errstate(divide="ignore", invalid="ignore"):
-            t = (off - o[axis]) / dw[..., axis]
-        hit = (t > 0) & (t < best_t)
-        if not hit.any():
-            continue
-        p = (o + dw[hit] * t[hit][:, None]) / _ROOM_TEXTURE_SCALE
-        ax = [k for k in range(3) if k != axis]
-        a, b = p[:, ax[0]], p[:, ax[1]]
-        val = 128.0 + 50.0 * np.sin(0.11 * a + pid) * np.cos(0.07 * b)
-        val += 80.0 * (_hash01(np.floor(a / 0.6), np.floor(b / 0.6), 11 + pid) - 0.5)
-        val += 50.0 * (_hash01(np.floor(a / 0.17), np.floor(b / 0.17), 23 + pid) - 0.5)
-        img[hit] = val
-        best_t[hit] = t[hit]
+    img, best_t = _cast_room(dw, o)
     rng = np.random.default_rng(seed_base + frame)
     img += rng.uniform(-noise, noise, img.shape)
     g = np.rint(img)
@@ -196,3 +202,31 @@ def rgbd_frame(cam: RGBDCamera, frame: int, seed_base: int = 9000, noise: float 
     z = np.where(np.isfinite(best_t) & (best_t <= _RGBD_RANGE), best_t, 0.0)  # t along (x, y, 1) is the depth
     depth = np.clip(np.rint(z * cam.depth_map_factor), 0, 65535).astype(np.uint16)
     return rgb, depth, Twc
+
+
+# ---- raw stereo (EuRoC-shaped: not rectified) -----------------------------------------------
+def raw_stereo_pair(rig, frame: int, seed_base: int = 12000, noise: float = 4.0):
+    """(left, right, Twc) raw u8 images of frame `frame` as a rig that is not factory-rectified
+    sees the RGB-D corridor (_ROOM, texture scale 0.25, 0.05 m/frame): rig = (left, right)
+    settings.RectifyCamera, Twc the pose of the rectified left camera.  The ray of a raw pixel is
+    R_c (its undistorted normalised point, the five iterations of _undistorted_rays with that
+    camera's K and D) in the rectified frame -- R_c takes raw camera coordinates to rectified ones,
+    so rectifying the pair (cv::initUndistortRectifyMap with R_c, P_c + cv::remap) gives the
+    pinhole views of LEFT.P / RIGHT.P.  The right camera sits bf / fx = -RIGHT.P[0,3] / RIGHT.P[0,0]
+    along the rectified x axis.  D has 4 or 5 coefficients (more raise: the inverse model here has
+    no k4..k6)."""
+    Twc = pose(frame, step=_RGBD_STEP)
+    baseline = -float(rig[1].P[0, 3]) / float(rig[1].P[0, 0])
+    out = []
+    for side, cam in enumerate(rig):
+        if len(np.asarray(cam.D).ravel()) > 5:  # _undistorted_rays inverts k1 k2 p1 p2 k3 only
+            raise ValueError("raw_stereo_pair renders cameras with at most 5 distortion coefficients")
+        K, D = np.asarray(cam.K, np.float64), tuple(float(v) for v in np.asarray(cam.D).ravel())
+        c = RGBDCamera(int(cam.cols), int(cam.rows), K[0, 0], K[1, 1], K[0, 2], K[1, 2], 0.0, D)
+        dw = (_undistorted_rays(c) @ np.asarray(cam.R, np.float64).T) @ Twc[:3, :3].T  # rows: d_rect = R d_raw
+        o = Twc[:3, 3] + Twc[:3, :3] @ np.array([baseline * side, 0.0, 0.0])
+        img, _ = _cast_room(dw, o)
+        rng = np.random.default_rng(seed_base + frame + 7919 * side)
+        img += rng.uniform(-noise, noise, img.shape)
+        out.append(np.clip(np.rint(img), 0, 255).astype(np.uint8))
+    return out[0], out[1], Twc
